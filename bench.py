@@ -2,12 +2,15 @@
 """bench.py -- rel_pose hot path on MI355X: image-pairs/sec, fwd+bwd, synthetic 384x384 pairs.
 
     python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus 1 --steps K --warmup W --full     (+ roofline, supplementary points, CPU baseline)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     (+ what the last timed step computed, as .npy)
 
 Workload (BASELINE.json metric / configs[2] shape, "train.py ... batch 64, 1xMI355X fwd+bwd" on the synthetic
 inputs of configs[1]): one train.py step = ViTEss.forward on [64,2,3,384,384] pairs per GPU (CNN front-end on
 MIOpen, ViT + Essential Matrix Module + regressor on this repo's HIP kernels) + geodesic loss + backward +
 (N>1: DDP gradient all-reduce over RCCL) + grad-clip + Adam step.  Inputs are resident in HBM before the timed
 region.  One JSON line on rank 0; see DESIGN.md "Measurement" for how `roofline` and `cpu_baseline` are formed.
+A plain run only sets up, warms up, times the K steps and prints the headline; everything else it can measure takes --full.
 """
 import argparse
 import json
@@ -32,6 +35,7 @@ PRECISIONS = {"fp32": 0, "split3": 3, "bf16": 1}
 FLOPS_FWD_PER_PAIR = 8588216320      # GEMM flops of the ViT+EMM+regressor hot path, forward
 METRIC = "image-pairs/sec fwd+bwd @384x384, 1/2/4/8 MI355X; R,t err vs ref"
 GRAPH_BELOW_PAIRS = 16               # single-GPU training steps at or below this many pairs replay captured HIP graphs by default
+DUMP_SAMPLE = 1 << 22                # --dump-outputs: elements of the 19.26 M trainable gradients written (16 MB)
 
 
 def model_args():
@@ -240,6 +244,23 @@ def supplementary_point(dev, tag, batch, hw, mode, precision, steps, warmup, tra
         ops.GEMM_PRECISION, ops.ATTN_BF16, ops.CNN_PRECISION, ops.TIMER = saved
 
 
+def dump_outputs(out_dir, poses, loss, params):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files.  Training steps also write their loss and the same
+    seeded sample of positions in the concatenation of the trainable parameters' gradients (model.parameters() order; after clipping,
+    as Adam consumed them)."""
+    import numpy as np
+    arrays = {"poses": poses}
+    if params:
+        grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params]).cpu()
+        idx = torch.arange(grads.numel())
+        if grads.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(grads.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+        arrays.update(loss=loss, grad_sample=grads[idx])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def parse_instance(text):
     """'1,1,1,3' -> (1,1,1,3) (an rp_gemm instance); anything else is a kernel tag of rel_pose_amd.ops.timed"""
     try:
@@ -331,10 +352,20 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="image pairs per GPU")
     ap.add_argument("--hw", type=int, default=384)
     ap.add_argument("--mode", default="train", choices=("train", "fwd"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: `roofline` (a survey of the step's own MFMA kernels, then HIP-event timing of the "
+                         "dominant one over the timed steps), `supplementary`, `cpu_baseline` and, for N>1, the step without the gradient "
+                         "exchange.  Without it the run only sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): poses (the pose "
+                         "estimates the forward returned); in training also loss and a fixed, seeded sample of %d of the trainable "
+                         "parameters' gradients (grad_sample).  Training then runs at learning rate 0: every step, the last one "
+                         "included, computes from the seeded inputs and initial weights, so every run and every build dump the same "
+                         "values up to rounding" % DUMP_SAMPLE)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--no-supplementary", action="store_true",
-                    help="skip the two extra bounded points (BASELINE configs[1] forward-only at 64 pairs, configs[4] bf16 at 128 pairs "
-                         "per GPU) that the default single-GPU run times after the headline loop and attaches as `supplementary`")
+                    help="with --full: skip the two extra bounded points (BASELINE configs[1] forward-only at 64 pairs, configs[4] bf16 at "
+                         "128 pairs per GPU) that a --full single-GPU run times after the headline loop and attaches as `supplementary`")
     ap.add_argument("--graph", action="store_true", default=None,
                     help="replay the step from captured HIP graphs (rel_pose_amd/graph.py) instead of launching eagerly.  Default: graphs "
                          "for single-GPU training at <= %d pairs per GPU -- there the ~350 launches of a step are host-bound when issued "
@@ -345,7 +376,7 @@ def main():
                     help="full = images -> CNN -> hot path (the metric); hot = synthetic CNN maps -> hot path only "
                          "(kernel profiling; not the headline number)")
     ap.add_argument("--timer-instance", default=None,
-                    help="kernel timed for `roofline`: default = the own MFMA kernel the step spends most time in, found by a survey of two "
+                    help="with --full, the kernel timed for `roofline`: default = the own MFMA kernel the step spends most time in, found by a survey of two "
                          "untimed steps (every tagged launch HIP-event-timed); or force a gemm_kernel<aL,bL,TM,TN> instance (\"1,1,1,3\") / a "
                          "kernel tag of ops.timed (\"dw192_f32\")")
     ap.add_argument("--precision", default="fp32", choices=tuple(PRECISIONS),
@@ -353,6 +384,10 @@ def main():
                          "three bf16 limbs per operand, six limb products on the bf16 MFMA pipe, fp32-grade results; "
                          "bf16 = operands rounded to bf16 (BASELINE.json configs[4]; NOT the headline metric)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.timer_instance is not None and not args.full:
+        ap.error("--timer-instance selects the `roofline` kernel, which only --full measures")
     if args.graph is None:
         args.graph = (args.mode == "train" and args.batch <= GRAPH_BELOW_PAIRS and int(os.environ.get("WORLD_SIZE", "1")) == 1
                       and args.scope == "full" and not os.environ.get("RP_BENCH_FORCE_DIST"))
@@ -401,8 +436,11 @@ def main():
     graphed = train and args.graph
     if graphed:
         net = model                                                    # the graphs do their own single flat all-reduce
-    # fused=True: the reference's torch.optim.Adam update (train.py:69) as one multi-tensor kernel instead of ~10
-    opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=5e-4, weight_decay=1e-5,
+    # fused=True: the reference's torch.optim.Adam update (train.py:69) as one multi-tensor kernel instead of ~10.  --dump-outputs: the
+    # same update at learning rate 0, so that the weights stay the seeded ones.  Some of MIOpen's convolutions sum split-K partials in
+    # run-dependent order; trained on, Adam turns those last-bit differences into visible ones within a few steps (20 steps: losses
+    # 4.7 and 7.4 in two runs), while a step from the same weights agrees from run to run to rounding.
+    opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=0.0 if args.dump_outputs else 5e-4, weight_decay=1e-5,
                            capturable=graphed, fused=True)
     images, poses, intr = synthetic_batch(args.batch, args.hw, dev, 1234 + rank)
     Ps = SE3(poses)
@@ -418,10 +456,17 @@ def main():
         def net(_images, Gs_, intrinsics=None):                          # noqa: F811
             return [SE3(model.forward_tokens(fmap, Gs_.data, i24))]
 
+    last_poses = [None]          # the latest forward's pose estimates (--dump-outputs); under graph capture, the graph's output buffer
+
+    def forward(im, G, it):
+        est = net(im, G, intrinsics=it)
+        last_poses[0] = est[0].data.detach()
+        return est
+
     def step():
         if train:
             opt.zero_grad(set_to_none=True)
-            est = net(images, Gs, intrinsics=intr.clone())
+            est = forward(images, Gs, intr.clone())
             ltr, lrot = geodesic_loss_tensors(Ps, est)
             loss = 10.0 * ltr + 10.0 * lrot
             loss.backward()
@@ -429,39 +474,42 @@ def main():
             opt.step()
             return loss
         with torch.no_grad():
-            return net(images, Gs, intrinsics=intr.clone())[0].data
+            return forward(images, Gs, intr.clone())[0].data
 
     ops.set_gemm_precision(PRECISIONS[args.precision])
     ops.set_attention_precision(1 if args.precision == "bf16" else 0)      # configs[4]: bf16 MFMA attention / EMM GEMMs too
     ops.set_cnn_precision(1 if args.precision == "bf16" and not os.environ.get("RP_BF16_KEEP_FP32_CNN") else 0)   # and the MIOpen convolutions
     nl = PRECISIONS[args.precision]
-    timer = ops.KernelTimer(parse_instance(args.timer_instance) if args.timer_instance else "none")
-    ops.TIMER = timer
+    timer = None                     # the `roofline` kernel's HIP-event timer (--full only)
+    if args.full:
+        timer = ops.KernelTimer(parse_instance(args.timer_instance) if args.timer_instance else "none")
+        ops.TIMER = timer
+        # The kernel timer is ON for the priming step: the first timed hipEventRecord on a stream switches its HSA queue to profiling mode
+        # and creates the runtime's signal pool (50-90 ms once, measured: 10 timed steps read 39-44 ms per step instead of 34.6 when that
+        # fell into the timed region)
+        timer.enabled = not os.environ.get("RP_NO_TIMER")
     eager_step = step
-    # untimed priming step, even with --warmup 0: lazy init and MIOpen's solver search never fall in the timed steps.  The kernel timer is ON
-    # for it: the first timed hipEventRecord on a stream switches its HSA queue to profiling mode and creates the runtime's signal pool
-    # (50-90 ms once, measured: 10 timed steps read 39-44 ms per step instead of 34.6 when that fell into the timed region)
-    timer.enabled = not os.environ.get("RP_NO_TIMER")
+    # untimed priming step, even with --warmup 0: lazy init and MIOpen's solver search never fall in the timed steps
     eager_step()
     torch.cuda.synchronize()
-    timer.enabled = False
-    timer.reset()
     survey = None
-    if args.timer_instance is None:
-        # which own kernel dominates THIS step on THIS box: two untimed steps, every tagged launch timed; `roofline` then follows it
-        dominant, survey = survey_kernels(eager_step, 2, nl)
-        if world > 1 or force_dist:      # every rank must time the same symbol: rank 0's choice
-            box = [dominant]
-            dist.broadcast_object_list(box, src=0)
-            dominant = box[0]
-        timer = ops.KernelTimer(dominant if dominant is not None else "none")
-        ops.TIMER = timer
+    if timer is not None:
+        timer.enabled = False
+        timer.reset()
+        if args.timer_instance is None:
+            # which own kernel dominates THIS step on THIS box: two untimed steps, every tagged launch timed; `roofline` then follows it
+            dominant, survey = survey_kernels(eager_step, 2, nl)
+            if world > 1 or force_dist:      # every rank must time the same symbol: rank 0's choice
+                box = [dominant]
+                dist.broadcast_object_list(box, src=0)
+                dominant = box[0]
+            timer = ops.KernelTimer(dominant if dominant is not None else "none")
+            ops.TIMER = timer
     if rank == 0 and not hot:
         rel_pose_amd._env.check_db()          # warns when the shipped MIOpen solver db does not belong to the loaded MIOpen
     if graphed:
         from rel_pose_amd.graph import GraphedTrainStep
-        fwd = (lambda im, G, it: net(im, G, intrinsics=it))
-        gs = GraphedTrainStep(model, opt, images, poses, intr, forward_fn=fwd).capture(warmup=max(args.warmup, 3))
+        gs = GraphedTrainStep(model, opt, images, poses, intr, forward_fn=forward).capture(warmup=max(args.warmup, 3))
         step = gs.step
     for _ in range(args.warmup):
         step()
@@ -479,7 +527,8 @@ def main():
     fence()
     if roctx is not None:
         roctx.roctxProfilerResume(0)
-    timer.enabled = not os.environ.get("RP_NO_TIMER")
+    if timer is not None:
+        timer.enabled = not os.environ.get("RP_NO_TIMER")
     t0 = time.perf_counter()
     last = None
     for _ in range(args.steps):
@@ -488,15 +537,19 @@ def main():
     el = time.perf_counter() - t0
     if roctx is not None:
         roctx.roctxProfilerPause(0)
-    timer.enabled = False
+    if timer is not None:
+        timer.enabled = False
+    if args.dump_outputs and rank == 0:       # before anything below runs more steps
+        trainable = [p for p in model.parameters() if p.requires_grad] if train else None
+        dump_outputs(args.dump_outputs, last_poses[0], last, trainable)
     dist_diag = None
     if world > 1 or force_dist:
-        # self-diagnosing scaling record: every rank's own time for the timed steps, and -- AFTER the timed
+        # self-diagnosing scaling record: every rank's own time for the timed steps, and (--full) -- AFTER the timed
         # region, never inside it -- the same step without the gradient exchange (DDP no_sync), so that the all-reduce time the
         # backward does not hide can be read off the line: exposed = ms_per_step - ms_per_step_no_allreduce (max over ranks each)
         el, per_rank = parallel.gather_step_times(el, args.steps, dev)
         dist_diag = {"per_rank_ms_per_step": per_rank}
-        if train and not graphed and hasattr(net, "no_sync"):
+        if args.full and train and not graphed and hasattr(net, "no_sync"):
             k = max(3, min(10, args.steps))
             # the probe runs whole steps (optimizer included) WITHOUT the gradient exchange: the replicas diverge.  Parameters, buffers and
             # the optimizer state are put back afterwards, so anything that runs later in this process sees consistent replicas.
@@ -528,7 +581,7 @@ def main():
                                       "buffers and optimizer state restored afterwards"})
     finite = bool(torch.isfinite(last).all())
 
-    if graphed:
+    if graphed and timer is not None:
         # per-kernel HIP events cannot be recorded inside a graph replay: time the roofline kernel over eager steps of the
         # SAME step function, same resident batch, right after the timed region (rocprofv3 over this command sees both)
         fence()
@@ -540,27 +593,7 @@ def main():
         fence()
         timer.enabled = False
     if rank == 0:
-        n_launch, t_launch, flops = timer.summary()
-        achieved = flops / max(n_launch, 1) / max(t_launch, 1e-12) / 1e12
         pairs = world * args.batch * args.steps
-        traffic, traffic_src, traffic_stale = None, None, None
-        kname = tag_symbol(timer.instance, nl)
-        # matrix-pipe ceiling of the timed kernel in ALGORITHMIC (2MNK) flops: the exact-fp32 MFMA peak, or the dense
-        # bf16 MFMA peak divided by the limb products issued per fp32 product (6 for split3, 1 for bf16)
-        peak = {0: FP32_MFMA_PEAK_TFLOPS, 3: BF16_MFMA_PEAK_TFLOPS / 6.0, 1: BF16_MFMA_PEAK_TFLOPS}[nl]
-        peak_note = {0: "fp32 MFMA peak (v_mfma_f32_32x32x2_f32)",
-                     3: "dense bf16 MFMA peak 2500 TF / 6 limb products per fp32 multiply-add (v_mfma_f32_32x32x16_bf16); "
-                        "the same kernel is %.2f of the 157.3 TF fp32-MFMA peak it replaces" % (achieved / FP32_MFMA_PEAK_TFLOPS),
-                     1: "dense bf16 MFMA peak"}[nl]
-        # PMC passes cannot run inside the timed process (tools/pmc_bench.sh); the committed passes of the matching operating point
-        # (64 pairs fp32 training / forward, 128 pairs bf16 training; bytes per launch of any other batch were not measured: null)
-        tfiles = None
-        if args.hw == 384:
-            if args.batch == 64 and nl == 0:
-                tfiles = TRAFFIC_FILES if train else ("r6_traffic_fwd.json", "r5_traffic_fwd.json", "r4_traffic_fwd.json", "r3_traffic_fwd.json")
-            elif args.batch == 128 and nl == 1 and train:
-                tfiles = ("r6_traffic_bf16.json", "r5_traffic_bf16.json", "r4_traffic_bf16.json", "r3_traffic_bf16.json")
-        traffic, traffic_src, traffic_stale = pmc_traffic(kname, tfiles) if tfiles else (None, None, None)
         rec = {
             "metric": METRIC, "value": round(pairs / el, 2), "unit": "image-pairs/sec", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * el / args.steps, 3),
@@ -578,21 +611,42 @@ def main():
                                                   "(v_mfma_f32_32x32x16_bf16) and the CNN front-end's MIOpen convolutions"}[nl],
                        "launch": "HIP graph replay (fwd+loss+bwd | flat grad all-reduce | clip+Adam)" if graphed else "eager",
                        "hot_path_share": "ViT+EMM+regressor on HIP kernels; ResNet front-end on MIOpen (SURVEY 8f-1)"},
-            "roofline": dict(roofline_of(flops / max(n_launch, 1), timer.bytes / max(n_launch, 1), t_launch, nl),
-                             peak_note=peak_note, traffic=traffic, traffic_unit="HBM bytes per launch (PMC)",
-                             traffic_source=traffic_src, traffic_stale=traffic_stale,
-                             algorithmic_bytes_per_launch_avg=timer.bytes / max(n_launch, 1), kernel=kname,
-                             kernel_chosen_by=("survey: largest total HIP-event time among the step's own MFMA kernels" if survey is not None
-                                               else "--timer-instance"),
-                             launches_timed=n_launch, avg_launch_us=round(t_launch * 1e6, 2),
-                             flops_per_launch_avg=flops / max(n_launch, 1),
-                             hot_path_frac=(survey or {}).get("hot_path_frac"),
-                             hot_path_tflops_whole_step=round((3 if train else 1) * FLOPS_FWD_PER_PAIR * pairs / el / 1e12, 2),
-                             survey=survey),
         }
-        if (world == 1 and not force_dist and not args.no_supplementary and train and args.scope == "full" and args.batch == 64
+        if timer is not None:
+            n_launch, t_launch, flops = timer.summary()
+            achieved = flops / max(n_launch, 1) / max(t_launch, 1e-12) / 1e12
+            traffic, traffic_src, traffic_stale = None, None, None
+            kname = tag_symbol(timer.instance, nl)
+            # matrix-pipe ceiling of the timed kernel in ALGORITHMIC (2MNK) flops: the exact-fp32 MFMA peak, or the dense
+            # bf16 MFMA peak divided by the limb products issued per fp32 product (6 for split3, 1 for bf16)
+            peak = {0: FP32_MFMA_PEAK_TFLOPS, 3: BF16_MFMA_PEAK_TFLOPS / 6.0, 1: BF16_MFMA_PEAK_TFLOPS}[nl]
+            peak_note = {0: "fp32 MFMA peak (v_mfma_f32_32x32x2_f32)",
+                         3: "dense bf16 MFMA peak 2500 TF / 6 limb products per fp32 multiply-add (v_mfma_f32_32x32x16_bf16); "
+                            "the same kernel is %.2f of the 157.3 TF fp32-MFMA peak it replaces" % (achieved / FP32_MFMA_PEAK_TFLOPS),
+                         1: "dense bf16 MFMA peak"}[nl]
+            # PMC passes cannot run inside the timed process (tools/pmc_bench.sh); the committed passes of the matching operating point
+            # (64 pairs fp32 training / forward, 128 pairs bf16 training; bytes per launch of any other batch were not measured: null)
+            tfiles = None
+            if args.hw == 384:
+                if args.batch == 64 and nl == 0:
+                    tfiles = TRAFFIC_FILES if train else ("r6_traffic_fwd.json", "r5_traffic_fwd.json", "r4_traffic_fwd.json", "r3_traffic_fwd.json")
+                elif args.batch == 128 and nl == 1 and train:
+                    tfiles = ("r6_traffic_bf16.json", "r5_traffic_bf16.json", "r4_traffic_bf16.json", "r3_traffic_bf16.json")
+            traffic, traffic_src, traffic_stale = pmc_traffic(kname, tfiles) if tfiles else (None, None, None)
+            rec["roofline"] = dict(roofline_of(flops / max(n_launch, 1), timer.bytes / max(n_launch, 1), t_launch, nl),
+                                   peak_note=peak_note, traffic=traffic, traffic_unit="HBM bytes per launch (PMC)",
+                                   traffic_source=traffic_src, traffic_stale=traffic_stale,
+                                   algorithmic_bytes_per_launch_avg=timer.bytes / max(n_launch, 1), kernel=kname,
+                                   kernel_chosen_by=("survey: largest total HIP-event time among the step's own MFMA kernels" if survey is not None
+                                                     else "--timer-instance"),
+                                   launches_timed=n_launch, avg_launch_us=round(t_launch * 1e6, 2),
+                                   flops_per_launch_avg=flops / max(n_launch, 1),
+                                   hot_path_frac=(survey or {}).get("hot_path_frac"),
+                                   hot_path_tflops_whole_step=round((3 if train else 1) * FLOPS_FWD_PER_PAIR * pairs / el / 1e12, 2),
+                                   survey=survey)
+        if (args.full and world == 1 and not force_dist and not args.no_supplementary and train and args.scope == "full" and args.batch == 64
                 and args.precision == "fp32" and not graphed):
-            # the default single-GPU run also times BASELINE configs[1] (forward only, 64 pairs) and configs[4]'s per-GPU workload
+            # a --full single-GPU run also times BASELINE configs[1] (forward only, 64 pairs) and configs[4]'s per-GPU workload
             # (bf16, 128 pairs) in this process, bounded to a few seconds each; the headline fields above are already final
             sup = {}         # (the headline model stays resident: 288 GB of HBM make freeing it pointless)
             for key, kw in (("fwd_only", dict(tag="ViTEss.forward, eval, no_grad, synthetic %dx%d pairs (BASELINE configs[1])" % (args.hw, args.hw),
@@ -609,7 +663,7 @@ def main():
             rec["supplementary"] = sup
         if dist_diag is not None:
             rec["distributed"] = dist_diag
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             rec["cpu_baseline"] = cpu_baseline(args.hw)
         print(json.dumps(rec), flush=True)
     if world > 1 or force_dist:

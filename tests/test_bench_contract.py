@@ -76,3 +76,29 @@ def test_committed_bench_line_names_the_dominant_kernel_of_the_committed_profile
             break
     assert first is not None
     assert kernel.replace("rpgemm::", "") in first.replace("rpgemm::", ""), (kernel, first)
+
+
+def test_dump_outputs_writes_the_same_float32_sample_every_time(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files within 64 MB; a gradient set larger than the sample is sampled at the same seeded
+    positions on every call, so two runs (or two builds) compare output for output"""
+    import sys
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n0 = 5000 * 1000
+    params = [torch.nn.Parameter(torch.zeros(5000, 1000)), torch.nn.Parameter(torch.zeros(7))]
+    params[0].grad = torch.arange(1, n0 + 1, dtype=torch.float32).view(5000, 1000)   # gradient = position + 1 (exact in float32)
+    outs = []                                                                         # params[1] has no gradient: zeros stand in
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.ones(3, 2, 7), torch.tensor(0.5), params)
+        outs.append({f[:-len(".npy")]: np.load(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))})
+    a, b = outs
+    assert set(a) == {"poses", "loss", "grad_sample"} and all(v.dtype == np.float32 for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    g = a["grad_sample"]
+    assert g.shape == (bench.DUMP_SAMPLE,) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    n = int((g > 0).sum())
+    assert n >= bench.DUMP_SAMPLE - 7 and np.all(g[n:] == 0)                         # the gradient-less tensor comes last
+    assert np.all(np.diff(g[:n]) > 0)                                                  # positions in order, each once

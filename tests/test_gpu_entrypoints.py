@@ -231,7 +231,8 @@ def test_bench_two_ranks_on_one_gpu():
     import json
     env = dict(os.environ, PYTHONPATH=ROOT, RP_BENCH_SHARE_GPU="1", RP_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8"]
+           "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -300,7 +301,7 @@ def test_bench_distributed_path_on_rccl_single_rank():
     env = dict(os.environ, PYTHONPATH=ROOT, RP_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29543",
                HSA_ENABLE_IPC_MODE_LEGACY="0", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -310,6 +311,33 @@ def test_bench_distributed_path_on_rccl_single_rank():
     assert len(d["per_rank_ms_per_step"]) == 1 and abs(d["per_rank_ms_per_step"][0] - rec["ms_per_step"]) < 1e-2
     assert d["ms_per_step_no_allreduce"] > 0 and d["gradient_bytes"] == 4 * 19258510
     assert abs(d["exposed_allreduce_ms"] - (rec["ms_per_step"] - d["ms_per_step_no_allreduce"])) < 1e-2
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and prints the headline line without the --full records;
+    --dump-outputs writes what its last timed step computed (here on the graph-replay path, the default at 8 pairs).  With the
+    weights held at the seeded ones, two runs of the same command agree to rounding however many steps they time."""
+    import json
+    import numpy as np
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+               "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["config"]["finite"] and rec["config"]["launch"].startswith("HIP graph")
+        assert abs(rec["value"] - 8 * 1e3 / rec["ms_per_step"]) < 1e-2 * rec["value"]
+        assert not {"roofline", "supplementary", "cpu_baseline"} & set(rec)
+        outs.append({f[:-len(".npy")]: np.load(str(tmp_path / run / f)) for f in os.listdir(str(tmp_path / run))})
+    a, b = outs
+    assert set(a) == {"poses", "loss", "grad_sample"}
+    assert a["poses"].shape == (8, 2, 7) and a["loss"].shape == () and a["grad_sample"].shape == (1 << 22,)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert np.abs(a["grad_sample"]).max() > 0 and np.abs(a["poses"]).max() > 0
+    assert abs(float(a["loss"]) - float(b["loss"])) < 1e-5 * abs(float(a["loss"]))
+    assert np.abs(a["poses"] - b["poses"]).max() < 1e-4
+    assert np.abs(a["grad_sample"] - b["grad_sample"]).max() < 1e-4 * np.abs(a["grad_sample"]).max()
 
 
 def test_graphed_train_step_matches_the_eager_step():

@@ -7,7 +7,7 @@ cp $L /tmp/keep.so
 for i in $(seq $R); do
   for v in A B; do
     cp rel_pose_amd/librelpose_hip_$v.so $L
-    ms=$(python bench.py --steps 30 --warmup 5 --no-supplementary --no-cpu-baseline "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'], d['roofline']['frac'])")
+    ms=$(python bench.py --full --steps 30 --warmup 5 --no-supplementary --no-cpu-baseline "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'], d['roofline']['frac'])")
     echo "round $i  [$v]  $ms"
   done
 done

@@ -3,7 +3,7 @@
 # round-2 end state: the other operating points of bench.py and the per-kernel timing tools (all 1 GPU)
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 $B --steps 300 --warmup 5 2>/dev/null | tail -1 > gpurun_out/pt_soak300.json
 $B --steps 30 --warmup 5 --batch 128 2>/dev/null | tail -1 > gpurun_out/pt_fp32_128pairs.json
 $B --steps 100 --warmup 10 --batch 128 --precision bf16 2>/dev/null | tail -1 > gpurun_out/pt_bf16_128pairs.json

@@ -31,8 +31,8 @@ python tools/show_stats.py $O/r3_bf16_128pairs_full_step_kernel_stats.csv 0 50 >
 } > $O/r3_late_fp32_ab.txt 2>&1
 {
   echo "# bench.py ms_per_step against --steps / --warmup, fresh process each (the kernel timer is primed in the untimed priming step; RP_NO_TIMER=1 = no timer at all)"
-  for cfg in "10 3" "20 5" "40 5" "100 20"; do set -- $cfg; python bench.py --steps $1 --warmup $2 --no-supplementary --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('steps $1 warmup $2:', d['ms_per_step'], 'ms/step', d['value'], 'pairs/s')"; done
-  RP_NO_TIMER=1 python bench.py --steps 20 --warmup 5 --no-supplementary --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('RP_NO_TIMER=1 steps 20 warmup 5:', d['ms_per_step'], 'ms/step', d['value'], 'pairs/s')"
+  for cfg in "10 3" "20 5" "40 5" "100 20"; do set -- $cfg; python bench.py --full --steps $1 --warmup $2 --no-supplementary --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('steps $1 warmup $2:', d['ms_per_step'], 'ms/step', d['value'], 'pairs/s')"; done
+  RP_NO_TIMER=1 python bench.py --full --steps 20 --warmup 5 --no-supplementary --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('RP_NO_TIMER=1 steps 20 warmup 5:', d['ms_per_step'], 'ms/step', d['value'], 'pairs/s')"
   echo "# tools/step_trace.py 40: GPU time of every step of a fresh process"
   timeout 200 python tools/step_trace.py 40 2>&1 | grep -v amdgpu.ids
   echo "# tools/host_phases.py: host enqueue time per phase at 6 pairs per GPU"

@@ -6,7 +6,7 @@ O=gpurun_out
 export PYTHONPATH=$PWD
 case "$1" in
 A)  # bench lines + step profiles
-  timeout 500 python bench.py --steps 40 --warmup 5 > $O/r5_bench.json 2> $O/r5_bench.err
+  timeout 500 python bench.py --full --steps 40 --warmup 5 > $O/r5_bench.json 2> $O/r5_bench.err
   timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r5_bench_driver_cmd.json 2>/dev/null
   timeout 300 bash tools/profile_step.sh r5_full_step 14 3 --steps 500 --warmup 3 --no-supplementary > /dev/null
   timeout 300 bash tools/profile_step.sh r5_hot_scope 8 3 --steps 500 --warmup 3 --scope hot --no-supplementary > /dev/null
@@ -25,7 +25,7 @@ C)  # other operating points + the test report
   for cfg in "bf16_128pairs:--steps 40 --warmup 5 --batch 128 --precision bf16" "fwd_only:--steps 100 --warmup 5 --mode fwd" "batch6:--steps 100 --warmup 10 --batch 6" \
              "bf16_128pairs_soak300:--steps 300 --warmup 5 --batch 128 --precision bf16"; do
     name=${cfg%%:*}; args=${cfg#*:}
-    timeout 300 python bench.py $args --no-supplementary --no-cpu-baseline > $O/r5_bench_$name.json 2>/dev/null
+    timeout 300 python bench.py --full $args --no-supplementary --no-cpu-baseline > $O/r5_bench_$name.json 2>/dev/null
   done
   Z=256 timeout 200 python tools/conv3x3_time.py 2>&1 | grep -v amdgpu.ids > $O/r5_conv3x3_time.txt
   rm -f $O/test_report.txt

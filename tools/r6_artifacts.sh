@@ -6,7 +6,7 @@ O=gpurun_out
 export PYTHONPATH=$PWD
 case "$1" in
 A)  # bench lines + step profiles
-  timeout 500 python bench.py --steps 40 --warmup 5 > $O/r6_bench.json 2> $O/r6_bench.err
+  timeout 500 python bench.py --full --steps 40 --warmup 5 > $O/r6_bench.json 2> $O/r6_bench.err
   timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r6_bench_driver_cmd.json 2>/dev/null
   timeout 300 bash tools/profile_step.sh r6_full_step 14 3 --steps 500 --warmup 3 --no-supplementary > /dev/null
   timeout 300 bash tools/profile_step.sh r6_hot_scope 8 3 --steps 500 --warmup 3 --scope hot --no-supplementary > /dev/null
@@ -27,7 +27,7 @@ C)  # other operating points + the test report
              "batch6:--steps 100 --warmup 10 --batch 6" "batch6_run2:--steps 100 --warmup 10 --batch 6" "batch6_run3:--steps 100 --warmup 10 --batch 6" \
              "batch6_eager:--steps 100 --warmup 10 --batch 6 --no-graph" "soak300:--steps 300 --warmup 5"; do
     name=${cfg%%:*}; args=${cfg#*:}
-    timeout 300 python bench.py $args --no-supplementary --no-cpu-baseline > $O/r6_bench_$name.json 2>/dev/null
+    timeout 300 python bench.py --full $args --no-supplementary --no-cpu-baseline > $O/r6_bench_$name.json 2>/dev/null
   done
   python tools/attn_p_time.py 2>&1 | grep -v amdgpu.ids > $O/r6_attn_stored_p_time.txt
   python tools/emm_s_time.py 2>&1 | grep -v amdgpu.ids > $O/r6_emm_stored_s_time.txt
