@@ -16,7 +16,7 @@ def essential_from_pose(poses):
     flat = poses.reshape(-1, 7).contiguous()
     _chk(flat)
     E = torch.empty(flat.shape[0], 3, 3, device=flat.device, dtype=torch.float32)
-    _lib.check(lib.rp_essential_from_pose(_p(flat), _p(E), flat.shape[0], _st()), "rp_essential_from_pose")
+    lib.rp_essential_from_pose(_p(flat), _p(E), flat.shape[0], _st())
     return E.view(*poses.shape[:-1], 3, 3)
 
 
@@ -29,7 +29,7 @@ def svd3x3(A):
     U = torch.empty(n, 3, 3, device=flat.device, dtype=torch.float32)
     S = torch.empty(n, 3, device=flat.device, dtype=torch.float32)
     V = torch.empty(n, 3, 3, device=flat.device, dtype=torch.float32)
-    _lib.check(lib.rp_svd3x3(_p(flat), _p(U), _p(S), _p(V), n, _st()), "rp_svd3x3")
+    lib.rp_svd3x3(_p(flat), _p(U), _p(S), _p(V), n, _st())
     lead = A.shape[:-2]
     return U.view(*lead, 3, 3), S.view(*lead, 3), V.view(*lead, 3, 3)
 
@@ -48,6 +48,5 @@ def pose_from_essential(E, x1, x2):
     pose = torch.empty(n, 7, device=Ef.device, dtype=torch.float32)
     count = torch.empty(n, device=Ef.device, dtype=torch.int32)
     import ctypes
-    _lib.check(lib.rp_pose_from_essential(_p(Ef), _p(x1f), _p(x2f), x1f.shape[1], _p(pose), ctypes.c_void_p(count.data_ptr()), n, _st()),
-               "rp_pose_from_essential")
+    lib.rp_pose_from_essential(_p(Ef), _p(x1f), _p(x2f), x1f.shape[1], _p(pose), ctypes.c_void_p(count.data_ptr()), n, _st())
     return pose, count

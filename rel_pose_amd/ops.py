@@ -384,7 +384,7 @@ class splitk_batch:
                 arr = (_lib.RpSplitkTask * len(chunk))()
                 for a, (ws, out, M, N, ldc, sk, tr) in zip(arr, chunk):
                     a.ws, a.C, a.M, a.N, a.ldc, a.split_k, a.trans_c = ws.data_ptr(), out.data_ptr(), M, N, ldc, sk, 1 if tr else 0
-                _lib.check(lib.rp_splitk_reduce_multi(arr, len(chunk), _st()), "rp_splitk_reduce_multi")
+                lib.rp_splitk_reduce_multi(arr, len(chunk), _st())
         return False
 
 
@@ -489,7 +489,7 @@ def gemm(A, B, M, N, K, *, a_layout=0, b_layout=0, lda=None, ldb=None, out=None,
         nby = batch * (M * K * float(A.element_size()) + 4.0 * N * K + M * N * (ob * (1 + (pre_out is not None))
                        + (float(aux.element_size()) if aux is not None else 0.0) + (4.0 if residual is not None else 0.0)))
         with timed(gemm_instance(M, N, a_layout, b_layout, aux is not None or residual is not None), 2.0 * M * N * K * batch, nby):
-            _lib.check(lib.rp_gemm(ctypes.byref(g), _st()), "rp_gemm")
+            lib.rp_gemm(ctypes.byref(g), _st())
         if defer is not None and g.split_k > 1:
             _sk_batch()[0].append(defer)
         return (out, colsum(cpart)) if want_colsum else out
@@ -498,7 +498,7 @@ def gemm(A, B, M, N, K, *, a_layout=0, b_layout=0, lda=None, ldb=None, out=None,
         # events are recorded by rp_gemm itself around the MAIN kernel (a split-K launch's reduce is a separate kernel)
         e0, e1 = tm.new_pair()
         g.ev_start, g.ev_stop = e0, e1
-        _lib.check(lib.rp_gemm(ctypes.byref(g), _st()), "rp_gemm")
+        lib.rp_gemm(ctypes.byref(g), _st())
         if defer is not None and g.split_k > 1:
             _sk_batch()[0].append(defer)
         tm.events.append((e0, e1))
@@ -507,7 +507,7 @@ def gemm(A, B, M, N, K, *, a_layout=0, b_layout=0, lda=None, ldb=None, out=None,
         tm.bytes += batch * (M * K * float(A.element_size()) + 4.0 * N * K + M * N * (ob * (1 + (pre_out is not None))
                              + (float(aux.element_size()) if aux is not None else 0.0) + (4.0 if residual is not None else 0.0)))
         return (out, colsum(cpart)) if want_colsum else out
-    _lib.check(lib.rp_gemm(ctypes.byref(g), _st()), "rp_gemm")
+    lib.rp_gemm(ctypes.byref(g), _st())
     if defer is not None and g.split_k > 1:
         _sk_batch()[0].append(defer)
     return (out, colsum(cpart)) if want_colsum else out
@@ -564,7 +564,7 @@ def transposed(w):
         o = torch.empty(t.shape[1], t.shape[0], device=t.device, dtype=torch.float32)
         a.src, a.dst, a.rows, a.cols = src.data_ptr(), o.data_ptr(), t.shape[0], t.shape[1]
         outs.append((t, src, o))
-    _lib.check(lib.rp_transpose_multi(arr, len(todo), _st()), "rp_transpose_multi")
+    lib.rp_transpose_multi(arr, len(todo), _st())
     for t, _, o in outs:
         try:
             t._rp_t = (t._version, t.data_ptr(), _PAD_GEN, o)
@@ -637,9 +637,8 @@ def linear_rows(x, W, b=None, act=0, want_pre=False, residual=None, ln=None, wan
     with timed("linear_rows_ln" if ln is not None else "linear_rows", 2.0 * M * N * K,
                4.0 * (M * K * (1 + (xn is not None)) + N * K + M * N * nmn)):
         wk = bf16_weight(W) if GEMM_PRECISION == 1 else W
-        _lib.check(lib.rp_linear_rows192(_p(x), _p(wk), _p(b), _p(residual), _p(g), _p(be), LN_EPS, _p(y), _p(pre), _p(xn), _p(mean),
-                                         _p(rstd), _p(dact_aux), _p(part), M, N, K, act, GEMM_PRECISION, io, _st()),
-                   "rp_linear_rows192")
+        lib.rp_linear_rows192(_p(x), _p(wk), _p(b), _p(residual), _p(g), _p(be), LN_EPS, _p(y), _p(pre), _p(xn), _p(mean),
+                              _p(rstd), _p(dact_aux), _p(part), M, N, K, act, GEMM_PRECISION, io, _st())
     out = ((y,) + ((pre,) if want_pre else ()) + ((xn, mean, rstd) if (ln is not None and want_ln_out) else ())
            + ((colsum(part),) if want_colsum else ()))
     return out[0] if len(out) == 1 else out
@@ -701,8 +700,7 @@ def linear_dx_lnbwd(dy, W, x, gamma, mean, rstd, add=None):
         dx = torch.empty_like(x)
         wt = bf16_weight(transposed(W))
         with timed("dx_lnbwd_bf16", 2.0 * M * N * DIM, M * (2.0 * N + 4.0 * DIM * (3 if add is not None else 2))):
-            _lib.check(lib.rp_dx_lnbwd_bf16(_p(dy), _p(wt), _p(x), _p(gamma), _p(mean), _p(rstd), _p(add), _p(dx), _p(part), M, N, _st()),
-                       "rp_dx_lnbwd_bf16")
+            lib.rp_dx_lnbwd_bf16(_p(dy), _p(wt), _p(x), _p(gamma), _p(mean), _p(rstd), _p(add), _p(dx), _p(part), M, N, _st())
         sums = colsum(part)
         if add is None:
             return dx, sums[:DIM], sums[DIM:]
@@ -738,21 +736,21 @@ def _dw192(a, b, out, trans):
     ws = _arena_take(nbytes, a.device, _sk_batch()[1]) if deferred else _workspace(nbytes, a.device)
     if f32 and DW_SPLIT3:
         with timed("dw192_split3", 2.0 * M * N * DIM, 4.0 * (M * (N + DIM) + sk * N * DIM)):
-            _lib.check(lib.rp_dw192_split3(_p(a), N, _p(b), M, N, _p(ws), nbytes, _st()), "rp_dw192_split3")
+            lib.rp_dw192_split3(_p(a), N, _p(b), M, N, _p(ws), nbytes, _st())
     elif f32:
         with timed("dw192_f32", 2.0 * M * N * DIM, 4.0 * (M * (N + DIM) + sk * N * DIM)):
-            _lib.check(lib.rp_dw192_f32(_p(a), N, _p(b), M, N, _p(ws), nbytes, _st()), "rp_dw192_f32")
+            lib.rp_dw192_f32(_p(a), N, _p(b), M, N, _p(ws), nbytes, _st())
     else:
         with timed("dw192_bf16" if b.dtype == torch.bfloat16 else "dw192_bf16_f32b", 2.0 * M * N * DIM,
                    M * (2.0 * N + b.element_size() * DIM) + 4.0 * sk * N * DIM):
-            _lib.check(lib.rp_dw192_bf16(_p(a), N, _p(b), 1 if b.dtype == torch.float32 else 0, M, N, _p(ws), nbytes, _st()), "rp_dw192_bf16")
+            lib.rp_dw192_bf16(_p(a), N, _p(b), 1 if b.dtype == torch.float32 else 0, M, N, _p(ws), nbytes, _st())
     task = (ws, out, N, DIM, N if trans else DIM, sk, trans)
     if deferred:
         _sk_batch()[0].append(task)
     else:
         arr = (_lib.RpSplitkTask * 1)()
         arr[0].ws, arr[0].C, arr[0].M, arr[0].N, arr[0].ldc, arr[0].split_k, arr[0].trans_c = ws.data_ptr(), out.data_ptr(), N, DIM, task[4], sk, 1 if trans else 0
-        _lib.check(lib.rp_splitk_reduce_multi(arr, 1, _st()), "rp_splitk_reduce_multi")
+        lib.rp_splitk_reduce_multi(arr, 1, _st())
     return out
 
 
@@ -822,7 +820,7 @@ def _colsum_multi(pairs):
         a.in_, a.rows, a.cols, a.ld, a.out = t.data_ptr(), t.shape[0], t.shape[1], t.shape[1], o.data_ptr()
     nbytes = lib.rp_colsum_multi_workspace_bytes(arr, len(pairs))
     ws = torch.empty(max(nbytes // 4, 1), device=pairs[0][0].device, dtype=torch.float32)
-    _lib.check(lib.rp_colsum_multi(arr, len(pairs), _p(ws), nbytes, _st()), "rp_colsum_multi")
+    lib.rp_colsum_multi(arr, len(pairs), _p(ws), nbytes, _st())
 
 
 def colsum(t2d):
@@ -839,7 +837,7 @@ def colsum(t2d):
         return out
     nbytes = lib.rp_colsum_workspace_bytes(rows, cols)
     ws = torch.empty(max(nbytes // 4, 1), device=t2d.device, dtype=torch.float32)
-    _lib.check(lib.rp_colsum(_p(t2d), rows, cols, cols, _p(out), _p(ws), nbytes, _st()), "rp_colsum")
+    lib.rp_colsum(_p(t2d), rows, cols, cols, _p(out), _p(ws), nbytes, _st())
     return out
 
 
@@ -850,8 +848,7 @@ def layernorm_fwd(x2d, gamma, beta, eps=LN_EPS, want_stats=True):
     y = torch.empty_like(x2d)
     mean = _empty(rows, like=x2d) if want_stats else None
     rstd = _empty(rows, like=x2d) if want_stats else None
-    _lib.check(lib.rp_layernorm_fwd(_p(x2d), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, C, eps, _st()),
-               "rp_layernorm_fwd")
+    lib.rp_layernorm_fwd(_p(x2d), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, C, eps, _st())
     return y, mean, rstd
 
 
@@ -864,8 +861,8 @@ def layernorm_bwd(dy, x2d, gamma, mean, rstd, add=None):
     np_ = 3 if add is not None else 2
     dx = torch.empty_like(x2d)
     part = _empty(nblk, np_ * C, like=x2d)
-    _lib.check(lib.rp_layernorm_bwd(_p(dy), _p(x2d), _p(gamma), _p(mean), _p(rstd), _p(add), _p(dx), _p(part),
-                                    None, rows, C, _st()), "rp_layernorm_bwd")
+    lib.rp_layernorm_bwd(_p(dy), _p(x2d), _p(gamma), _p(mean), _p(rstd), _p(add), _p(dx), _p(part),
+                         None, rows, C, _st())
     sums = colsum(part)                                 # one launch: [dgamma | dbeta (| colsum(add))]
     if add is None:
         return dx, sums[:C], sums[C:]
@@ -896,14 +893,13 @@ def attn_fwd(qkv, Z, stats_only=False, q_off=0, k_off=DIM, v_off=2 * DIM, q_xor=
         pst = _empty(Z, HEADS, N_TOK // 32, N_TOK // 32, 1024, like=qkv)
         mrun = _empty(Z, HEADS, N_TOK // 32, N_TOK, like=qkv)
         with timed("attn_fwd_savep", 4.0 * Z * HEADS * N_TOK * N_TOK * hd, 4.0 * Z * N_TOK * (4 * DIM + HEADS * (N_TOK + 19))):
-            _lib.check(lib.rp_attn_fwd_savep(P(base + 4 * q_off), P(base + 4 * k_off), P(base + 4 * v_off), _p(o), _p(lse), _p(pst),
-                                             _p(mrun), Z, HEADS, ld, ld, ld, DIM, hd ** -0.5, _st()), "rp_attn_fwd_savep")
+            lib.rp_attn_fwd_savep(P(base + 4 * q_off), P(base + 4 * k_off), P(base + 4 * v_off), _p(o), _p(lse), _p(pst),
+                                  _p(mrun), Z, HEADS, ld, ld, ld, DIM, hd ** -0.5, _st())
         return o, lse, pst, mrun
     with timed("attn_stats" if stats_only else "attn_fwd", (2.0 if stats_only else 4.0) * Z * HEADS * N_TOK * N_TOK * hd,
                4.0 * Z * N_TOK * ((2 if stats_only else 4) * DIM + HEADS)):
-        _lib.check(lib.rp_attn_fwd(P(base + 4 * q_off), P(base + 4 * k_off), P(base + 4 * v_off), _p(o), _p(lse), Z, HEADS,
-                                   ld, ld, ld, DIM, q_xor, k_xor, hd ** -0.5, 1 if stats_only else 0, ATTN_BF16, _st()),
-                   "rp_attn_fwd")
+        lib.rp_attn_fwd(P(base + 4 * q_off), P(base + 4 * k_off), P(base + 4 * v_off), _p(o), _p(lse), Z, HEADS,
+                        ld, ld, ld, DIM, q_xor, k_xor, hd ** -0.5, 1 if stats_only else 0, ATTN_BF16, _st())
     return o, lse
 
 
@@ -922,9 +918,8 @@ def attn_fwd_bf16(qkv, Z, stats_only=False, q_off=0, k_off=DIM, v_off=2 * DIM, q
     hd = DIM // HEADS
     with timed("attn_stats_bf16" if stats_only else "attn_fwd_bf16", (2.0 if stats_only else 4.0) * Z * HEADS * N_TOK * N_TOK * hd,
                2.0 * Z * N_TOK * ((2 if stats_only else 4) * DIM) + 4.0 * Z * N_TOK * HEADS):
-        _lib.check(lib.rp_attn_fwd_bf16(P(base + 2 * q_off), P(base + 2 * k_off), P(base + 2 * v_off), _p(o), _p(lse), Z, HEADS,
-                                        ld, ld, ld, DIM, q_xor, k_xor, hd ** -0.5, 1 if stats_only else 0, _st()),
-                   "rp_attn_fwd_bf16")
+        lib.rp_attn_fwd_bf16(P(base + 2 * q_off), P(base + 2 * k_off), P(base + 2 * v_off), _p(o), _p(lse), Z, HEADS,
+                             ld, ld, ld, DIM, q_xor, k_xor, hd ** -0.5, 1 if stats_only else 0, _st())
     return o, lse
 
 
@@ -939,7 +934,7 @@ def attn_bwd_bf16(qkv, o, lse2, do, Z, kv_xor=0, want_bias_partials=False):
     _chk(lse2)
     ld = qkv.shape[1]
     delta = torch.empty(Z, HEADS, N_TOK, device=qkv.device, dtype=torch.float32)
-    _lib.check(lib.rp_attn_bwd_delta_bf16(_p(do), _p(o), _p(delta), Z, HEADS, DIM, _st()), "rp_attn_bwd_delta_bf16")
+    lib.rp_attn_bwd_delta_bf16(_p(do), _p(o), _p(delta), Z, HEADS, DIM, _st())
     dqkv = torch.empty_like(qkv)
     P = ctypes.c_void_p
     b, d = qkv.data_ptr(), dqkv.data_ptr()
@@ -949,10 +944,10 @@ def attn_bwd_bf16(qkv, o, lse2, do, Z, kv_xor=0, want_bias_partials=False):
         pb = part.data_ptr()
     hd = DIM // HEADS
     with timed("attn_bwd_bf16", 14.0 * Z * HEADS * N_TOK * N_TOK * hd, 2.0 * Z * N_TOK * 8 * DIM):
-        _lib.check(lib.rp_attn_bwd_bf16(P(b), P(b + 2 * DIM), P(b + 4 * DIM), _p(do), _p(lse2), _p(delta), P(d), P(d + 2 * DIM),
-                                        P(d + 4 * DIM), Z, HEADS, ld, ld, ld, DIM, ld, ld, ld, hd ** -0.5, kv_xor,
-                                        P(pb) if pb else None, P(pb + 4 * DIM) if pb else None, P(pb + 8 * DIM) if pb else None,
-                                        3 * DIM, _st()), "rp_attn_bwd_bf16")
+        lib.rp_attn_bwd_bf16(P(b), P(b + 2 * DIM), P(b + 4 * DIM), _p(do), _p(lse2), _p(delta), P(d), P(d + 2 * DIM),
+                             P(d + 4 * DIM), Z, HEADS, ld, ld, ld, DIM, ld, ld, ld, hd ** -0.5, kv_xor,
+                             P(pb) if pb else None, P(pb + 4 * DIM) if pb else None, P(pb + 8 * DIM) if pb else None,
+                             3 * DIM, _st())
     return (dqkv, part) if want_bias_partials else dqkv
 
 
@@ -973,8 +968,8 @@ def ds_matmul(ds, b_base, ldb, out_base, ldo, Z, b_xor=0, colpart_base=None, ldp
     _chk_act(ds)
     bf = int(ds.dtype == torch.bfloat16)
     with timed("ds_matmul", 2.0 * Z * HEADS * N_TOK * N_TOK * 64, Z * HEADS * N_TOK * ((2.0 if bf else 4.0) * N_TOK + 4.0 * 128)):
-        _lib.check(lib.rp_ds_matmul(_p(ds), ctypes.c_void_p(b_base), ctypes.c_void_p(out_base), Z, HEADS, ldb, ldo, b_xor, bf,
-                                    ctypes.c_void_p(colpart_base) if colpart_base else None, ldp, _st()), "rp_ds_matmul")
+        lib.rp_ds_matmul(_p(ds), ctypes.c_void_p(b_base), ctypes.c_void_p(out_base), Z, HEADS, ldb, ldo, b_xor, bf,
+                         ctypes.c_void_p(colpart_base) if colpart_base else None, ldp, _st())
 
 
 QKV_BIAS_FROM_PRODUCERS = True      # A/B aid
@@ -989,7 +984,7 @@ def attn_bwd(qkv, o, lse, do, Z, fork=None, kv_xor=0, want_bias_partials=False, 
     _chk(qkv, o, lse, do)
     ld = qkv.shape[1]
     delta = _empty(Z, HEADS, N_TOK, like=qkv)
-    _lib.check(lib.rp_attn_bwd_delta(_p(do), _p(o), _p(delta), Z, HEADS, DIM, _st()), "rp_attn_bwd_delta")
+    lib.rp_attn_bwd_delta(_p(do), _p(o), _p(delta), Z, HEADS, DIM, _st())
     dqkv = torch.empty_like(qkv)
     P = ctypes.c_void_p
     b, d = qkv.data_ptr(), dqkv.data_ptr()
@@ -1006,18 +1001,15 @@ def attn_bwd(qkv, o, lse, do, Z, fork=None, kv_xor=0, want_bias_partials=False, 
             pb = part.data_ptr()
         hd = DIM // HEADS
         with timed("attn_bwd_dkdv_p", 6.0 * Z * HEADS * N_TOK * N_TOK * hd, 4.0 * Z * (N_TOK * 5 * DIM + HEADS * N_TOK * (2 * N_TOK + 21))):
-            _lib.check(lib.rp_attn_bwd_dkdv_p(P(b), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), _p(pst), _p(mrun), P(d + 4 * DIM),
-                                              P(d + 8 * DIM), _p(ds), Z, HEADS, ld, ld, DIM, ld, ld, sc,
-                                              P(pb + 4 * DIM) if pb else None, P(pb + 8 * DIM) if pb else None, 3 * DIM, _st()),
-                       "rp_attn_bwd_dkdv_p")
+            lib.rp_attn_bwd_dkdv_p(P(b), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), _p(pst), _p(mrun), P(d + 4 * DIM),
+                                   P(d + 8 * DIM), _p(ds), Z, HEADS, ld, ld, DIM, ld, ld, sc,
+                                   P(pb + 4 * DIM) if pb else None, P(pb + 8 * DIM) if pb else None, 3 * DIM, _st())
         with timed("ds_matmul_t", 2.0 * Z * HEADS * N_TOK * N_TOK * hd, Z * HEADS * N_TOK * (4.0 * N_TOK + 4.0 * 128)):
-            _lib.check(lib.rp_ds_matmul_t(_p(ds), P(b + 4 * DIM), P(d), Z, HEADS, ld, ld, 0, P(pb) if pb else None, 3 * DIM, _st()),
-                       "rp_ds_matmul_t")                                             # dQ = dS K
+            lib.rp_ds_matmul_t(_p(ds), P(b + 4 * DIM), P(d), Z, HEADS, ld, ld, 0, P(pb) if pb else None, 3 * DIM, _st())   # dQ = dS K
         return (dqkv, part) if want_bias_partials else dqkv
     if kv_xor:
-        _lib.check(lib.rp_attn_bwd_cross(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d),
-                                         P(d + 4 * DIM), P(d + 8 * DIM), Z, HEADS, ld, ld, ld, DIM, ld, ld, ld, sc, 1, ATTN_BF16, _st()),
-                   "rp_attn_bwd_cross")
+        lib.rp_attn_bwd_cross(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d),
+                              P(d + 4 * DIM), P(d + 8 * DIM), Z, HEADS, ld, ld, ld, DIM, ld, ld, ld, sc, 1, ATTN_BF16, _st())
         return (dqkv, None) if want_bias_partials else dqkv
     if ATTN_BWD_STORE_DS and (fork is None or not fork.enabled):
         # the dK/dV pass stores scale*dS ([Z,H,576,576] in 32x32 tiles; fp32, bf16 in the bf16 configuration); dQ = dS K is then one
@@ -1033,24 +1025,23 @@ def attn_bwd(qkv, o, lse, do, Z, fork=None, kv_xor=0, want_bias_partials=False, 
         # (algorithmic flops: dV, dP, dK -- the S recompute the kernel also executes is not counted)
         with timed("attn_bwd_dkdv_ds", 6.0 * Z * HEADS * N_TOK * N_TOK * hd,
                    (2.0 if ATTN_BF16 else 4.0) * Z * HEADS * N_TOK * N_TOK + 4.0 * Z * N_TOK * (6 * DIM + 2 * HEADS)):
-            _lib.check(lib.rp_attn_bwd_dkdv_ds(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d + 4 * DIM),
-                                               P(d + 8 * DIM), _p(ds), Z, HEADS, ld, ld, ld, DIM, ld, ld, sc, ATTN_BF16,
-                                               P(pb + 4 * DIM) if pb else None, P(pb + 8 * DIM) if pb else None, 3 * DIM, _st()),
-                       "rp_attn_bwd_dkdv_ds")
+            lib.rp_attn_bwd_dkdv_ds(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d + 4 * DIM),
+                                    P(d + 8 * DIM), _p(ds), Z, HEADS, ld, ld, ld, DIM, ld, ld, sc, ATTN_BF16,
+                                    P(pb + 4 * DIM) if pb else None, P(pb + 8 * DIM) if pb else None, 3 * DIM, _st())
         ds_matmul(ds, b + 4 * DIM, ld, d, ld, Z, colpart_base=pb, ldp=3 * DIM)      # dQ = dS K: one streaming launch
         return (dqkv, part) if want_bias_partials else dqkv
     if fork is None or not fork.enabled:
-        _lib.check(lib.rp_attn_bwd(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d), P(d + 4 * DIM),
-                                   P(d + 8 * DIM), Z, HEADS, ld, ld, ld, DIM, ld, ld, ld, sc, ATTN_BF16, _st()), "rp_attn_bwd")
+        lib.rp_attn_bwd(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d), P(d + 4 * DIM),
+                        P(d + 8 * DIM), Z, HEADS, ld, ld, ld, DIM, ld, ld, ld, sc, ATTN_BF16, _st())
         return (dqkv, None) if want_bias_partials else dqkv
     fork.sync_side()                                   # delta (and do, dqkv allocation) visible to the side stream
 
     def dq_pass():
-        _lib.check(lib.rp_attn_bwd_dq(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d), Z, HEADS,
-                                      ld, ld, ld, DIM, ld, sc, ATTN_BF16, _st()), "rp_attn_bwd_dq")
+        lib.rp_attn_bwd_dq(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d), Z, HEADS,
+                           ld, ld, ld, DIM, ld, sc, ATTN_BF16, _st())
     fork.on_side(dq_pass)
-    _lib.check(lib.rp_attn_bwd_dkdv(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d + 4 * DIM),
-                                    P(d + 8 * DIM), Z, HEADS, ld, ld, ld, DIM, ld, ld, sc, ATTN_BF16, _st()), "rp_attn_bwd_dkdv")
+    lib.rp_attn_bwd_dkdv(P(b), P(b + 4 * DIM), P(b + 8 * DIM), _p(do), _p(lse), _p(delta), P(d + 4 * DIM),
+                         P(d + 8 * DIM), Z, HEADS, ld, ld, ld, DIM, ld, ld, sc, ATTN_BF16, _st())
     return (dqkv, None) if want_bias_partials else dqkv
 
 
@@ -1064,7 +1055,7 @@ def preprocess(images, pad=0):
     Z = B * two
     side = 224 + 2 * pad
     out = torch.empty(Z, side, side, 3, device=images.device, dtype=torch.float32)
-    _lib.check(lib.rp_preprocess_padded(_p(images), _p(out), Z, H, W, pad, _st()), "rp_preprocess_padded")
+    lib.rp_preprocess_padded(_p(images), _p(out), Z, H, W, pad, _st())
     return out if pad else out.permute(0, 3, 1, 2)          # pad = 0: [Z,3,224,224] view with channels-last strides
 
 
@@ -1083,7 +1074,7 @@ def posenc(intrinsics, B, device, l1=False):
     lib = _lib.load()
     _chk(intrinsics)
     pos = torch.empty(B, N_TOK, 6, device=device, dtype=torch.float32)
-    _lib.check(lib.rp_posenc(_p(intrinsics), _p(lin24(device)), _p(pos), B, 1 if l1 else 0, _st()), "rp_posenc")
+    lib.rp_posenc(_p(intrinsics), _p(lin24(device)), _p(pos), B, 1 if l1 else 0, _st())
     return pos
 
 
@@ -1091,7 +1082,7 @@ def emm_build_x(qkv, pos, Z):
     lib = _lib.load()
     _chk(qkv, pos)
     x = _empty(Z, HEADS, N_TOK, XW, like=qkv)
-    _lib.check(lib.rp_emm_build_x(_p(qkv), _p(pos), _p(x), Z, HEADS, qkv.shape[1], _st()), "rp_emm_build_x")
+    lib.rp_emm_build_x(_p(qkv), _p(pos), _p(x), Z, HEADS, qkv.shape[1], _st())
     return x
 
 
@@ -1129,8 +1120,8 @@ def emm_stats(qkv, Z, single=False, want_s=False):
     s = _empty(Z, HEADS, N_TOK // 32, N_TOK // 32, 1024, like=qkv) if (want_s and EMM_STORE_S and not ATTN_BF16) else None
     with timed("emm_stats", 2.0 * Z * HEADS * N_TOK * N_TOK * 64,
                4.0 * Z * N_TOK * (2 * DIM + 2 * HEADS) + (4.0 * Z * HEADS * N_TOK * N_TOK if s is not None else 0.0)):
-        _lib.check(lib.rp_emm_stats(ctypes.c_void_p(b), ctypes.c_void_p(b + 4 * DIM), _p(rlse), _p(clse), _p(ws), _p(s), Z, HEADS, ld, ld,
-                                    (DIM // HEADS) ** -0.5, ATTN_BF16, _st()), "rp_emm_stats")
+        lib.rp_emm_stats(ctypes.c_void_p(b), ctypes.c_void_p(b + 4 * DIM), _p(rlse), _p(clse), _p(ws), _p(s), Z, HEADS, ld, ld,
+                         (DIM // HEADS) ** -0.5, ATTN_BF16, _st())
     return (rlse, clse, s) if want_s else (rlse, clse)
 
 
@@ -1149,15 +1140,15 @@ def emm_apply(qkv, x, rlse, clse, Z, swap=False, want_t=True, want_f=True, singl
     with timed("emm_apply_s" if s is not None else "emm_apply",
                2.0 * Z * HEADS * (N_TOK * N_TOK * ((0 if s is not None else 64) + XW) + (N_TOK * XW * XW if f is not None else 0)),
                4.0 * Z * HEADS * N_TOK * ((N_TOK if s is not None else 2 * 64) + 2 * XW + 2)):
-        _lib.check(lib.rp_emm_apply(_p(qkv), qkv.shape[1], _p(x), _p(x_left), _p(rlse), _p(clse), _p(s), _p(t), _p(f), Z, HEADS,
-                                    (DIM // HEADS) ** -0.5, 1 if swap else 0, 1 if single else 0, ATTN_BF16, _st()), "rp_emm_apply")
+        lib.rp_emm_apply(_p(qkv), qkv.shape[1], _p(x), _p(x_left), _p(rlse), _p(clse), _p(s), _p(t), _p(f), Z, HEADS,
+                         (DIM // HEADS) ** -0.5, 1 if swap else 0, 1 if single else 0, ATTN_BF16, _st())
     return t, f
 
 
 def emm_finalize(fpart, Z):
     lib = _lib.load()
     g = _empty(Z * 70, GW, like=fpart)
-    _lib.check(lib.rp_emm_finalize(_p(fpart), _p(g), Z, HEADS, GW, _st()), "rp_emm_finalize")
+    lib.rp_emm_finalize(_p(fpart), _p(g), Z, HEADS, GW, _st())
     return g
 
 
@@ -1165,7 +1156,7 @@ def emm_finalize_bwd(dg, Z):
     lib = _lib.load()
     _chk(dg)
     df = _empty(Z, HEADS, XW, XW, like=dg)
-    _lib.check(lib.rp_emm_finalize_bwd(_p(dg), _p(df), Z, HEADS, GW, _st()), "rp_emm_finalize_bwd")
+    lib.rp_emm_finalize_bwd(_p(dg), _p(df), Z, HEADS, GW, _st())
     return df
 
 
@@ -1174,7 +1165,7 @@ def rowdot96(a, b):
     _chk(a, b)
     rows = a.numel() // XW
     out = _empty(*a.shape[:-1], like=a)
-    _lib.check(lib.rp_rowdot96(_p(a), _p(b), _p(out), rows, _st()), "rp_rowdot96")
+    lib.rp_rowdot96(_p(a), _p(b), _p(out), rows, _st())
     return out
 
 
@@ -1210,21 +1201,21 @@ def emm_backward(qkv, x, t, rlse, clse, df, Z, single=False, cross=False, s=None
         # algorithmic: S recompute is not counted; dA = W X^T (96) and dq = dS k (64) per score element
         with timed("emm_grad_ds_s" if s is not None else "emm_grad_ds", 2.0 * Z * HEADS * N_TOK * N_TOK * (XW + 64),
                    4.0 * Z * HEADS * N_TOK * ((2 if s is not None else 1) * N_TOK + 3 * 64 + 2 * XW + 4)):
-            _lib.check(lib.rp_emm_grad_ds(_p(qkv), ld, _p(x), _p(w), _p(rlse), _p(clse), _p(rho), _p(gam), _p(s), _p(dqkv), _p(ds), Z,
-                                          HEADS, scale, sg, ATTN_BF16, _st()), "rp_emm_grad_ds")
+            lib.rp_emm_grad_ds(_p(qkv), ld, _p(x), _p(w), _p(rlse), _p(clse), _p(rho), _p(gam), _p(s), _p(dqkv), _p(ds), Z,
+                               HEADS, scale, sg, ATTN_BF16, _st())
         # dk_z = dS_z (key-major tiles) x q_{z^1}: one streaming launch (the stored-S pass writes the 16-byte-run tiles rp_ds_matmul_t takes)
         if s is not None:
             with timed("ds_matmul_t", 2.0 * Z * HEADS * N_TOK * N_TOK * 64, Z * HEADS * N_TOK * (4.0 * N_TOK + 4.0 * 128)):
-                _lib.check(lib.rp_ds_matmul_t(_p(ds), ctypes.c_void_p(qkv.data_ptr()), ctypes.c_void_p(dqkv.data_ptr() + 4 * DIM), Z, HEADS,
-                                              ld, ld, 1, None, 0, _st()), "rp_ds_matmul_t")
+                lib.rp_ds_matmul_t(_p(ds), ctypes.c_void_p(qkv.data_ptr()), ctypes.c_void_p(dqkv.data_ptr() + 4 * DIM), Z, HEADS,
+                                   ld, ld, 1, None, 0, _st())
         else:
             ds_matmul(ds, qkv.data_ptr(), ld, dqkv.data_ptr() + 4 * DIM, ld, Z, b_xor=1)
     else:
-        _lib.check(lib.rp_emm_grad(_p(qkv), ld, _p(x), _p(w), _p(rlse), _p(clse), _p(rho), _p(gam), _p(dqkv), Z, HEADS,
-                                   scale, 0, sg, ATTN_BF16, _st()), "rp_emm_grad(q)")
-        _lib.check(lib.rp_emm_grad(_p(qkv), ld, _p(xl), _p(wp), _p(rlse), _p(clse), _p(rho), _p(gam), _p(dqkv), Z, HEADS,
-                                   scale, 1, sg, ATTN_BF16, _st()), "rp_emm_grad(k)")
-    _lib.check(lib.rp_emm_build_x_bwd(_p(dx), _p(dqkv), Z, HEADS, ld, _st()), "rp_emm_build_x_bwd")
+        lib.rp_emm_grad(_p(qkv), ld, _p(x), _p(w), _p(rlse), _p(clse), _p(rho), _p(gam), _p(dqkv), Z, HEADS,
+                        scale, 0, sg, ATTN_BF16, _st())
+        lib.rp_emm_grad(_p(qkv), ld, _p(xl), _p(wp), _p(rlse), _p(clse), _p(rho), _p(gam), _p(dqkv), Z, HEADS,
+                        scale, 1, sg, ATTN_BF16, _st())
+    lib.rp_emm_build_x_bwd(_p(dx), _p(dqkv), Z, HEADS, ld, _st())
     return dqkv
 
 
@@ -1245,14 +1236,14 @@ def emm_forward_bf16(qkv, pos, Z, want_t=True):
     _, rlse2 = attn_fwd_bf16(qkv, Z, stats_only=True, q_off=0, k_off=DIM, q_xor=1, k_xor=0)          # rows i: queries of the partner image
     _, clse2 = attn_fwd_bf16(qkv, Z, stats_only=True, q_off=DIM, k_off=0, q_xor=0, k_xor=1)          # columns j: keys as the owner rows
     xa = _bf(Z, HEADS, N_TOK, XW, like=qkv)
-    _lib.check(lib.rp_emm_build_x_bf16(_p(qkv), _p(pos), _p(xa), Z, HEADS, ld, _st()), "rp_emm_build_x_bf16")
+    lib.rp_emm_build_x_bf16(_p(qkv), _p(pos), _p(xa), Z, HEADS, ld, _st())
     t = _bf(Z, HEADS, N_TOK, XW, like=qkv)
     with timed("emm_apply_bf16", 2.0 * Z * HEADS * N_TOK * N_TOK * (64 + XW), 2.0 * Z * HEADS * N_TOK * (2 * 64 + 2 * XW)):
-        _lib.check(lib.rp_emm_apply_bf16(_p(qkv), ld, _p(xa), _p(rlse2), _p(clse2), _p(t), Z, HEADS, sc, 0, _st()), "rp_emm_apply_bf16")
+        lib.rp_emm_apply_bf16(_p(qkv), ld, _p(xa), _p(rlse2), _p(clse2), _p(t), Z, HEADS, sc, 0, _st())
     f = torch.empty(Z, HEADS, XW, XW, device=qkv.device, dtype=torch.float32)
-    _lib.check(lib.rp_emm_f_bf16(_p(xa), _p(t), _p(f), Z, HEADS, _st()), "rp_emm_f_bf16")
+    lib.rp_emm_f_bf16(_p(xa), _p(t), _p(f), Z, HEADS, _st())
     g = _empty(Z * 70, GW, like=f)
-    _lib.check(lib.rp_emm_finalize_parts(_p(f), _p(g), Z, HEADS, GW, 1, _st()), "rp_emm_finalize_parts")
+    lib.rp_emm_finalize_parts(_p(f), _p(g), Z, HEADS, GW, 1, _st())
     return g, (xa, t, rlse2, clse2)
 
 
@@ -1266,16 +1257,14 @@ def emm_backward_bf16(qkv, xa, t, rlse2, clse2, df, Z):
     w, wp = _bf(Z, HEADS, N_TOK, XW, like=qkv), _bf(Z, HEADS, N_TOK, XW, like=qkv)
     rho = torch.empty(Z, HEADS, N_TOK, device=qkv.device, dtype=torch.float32)
     gam = torch.empty_like(rho)
-    _lib.check(lib.rp_emm_w_bf16(_p(xa), _p(t), _p(df), _p(w), _p(wp), _p(rho), Z, HEADS, _st()), "rp_emm_w_bf16")
+    lib.rp_emm_w_bf16(_p(xa), _p(t), _p(df), _p(w), _p(wp), _p(rho), Z, HEADS, _st())
     u = _bf(Z, HEADS, N_TOK, XW, like=qkv)
-    _lib.check(lib.rp_emm_apply_bf16(_p(qkv), ld, _p(xa), _p(rlse2), _p(clse2), _p(u), Z, HEADS, sc, 1, _st()), "rp_emm_apply_bf16(swap)")
+    lib.rp_emm_apply_bf16(_p(qkv), ld, _p(xa), _p(rlse2), _p(clse2), _p(u), Z, HEADS, sc, 1, _st())
     dqkv = torch.empty_like(qkv)
-    _lib.check(lib.rp_emm_dx_bf16(_p(t), _p(u), _p(wp), _p(df), _p(dqkv), ld, _p(gam), Z, HEADS, _st()), "rp_emm_dx_bf16")
+    lib.rp_emm_dx_bf16(_p(t), _p(u), _p(wp), _p(df), _p(dqkv), ld, _p(gam), Z, HEADS, _st())
     with timed("emm_grad_bf16", 2.0 * Z * HEADS * N_TOK * N_TOK * (64 + XW + 64), 2.0 * Z * HEADS * N_TOK * (3 * 64 + 2 * XW)):
-        _lib.check(lib.rp_emm_grad_bf16(_p(qkv), ld, _p(xa), _p(w), _p(rlse2), _p(clse2), _p(rho), _p(gam), _p(dqkv), Z, HEADS, sc, 0, _st()),
-                   "rp_emm_grad_bf16(q)")
-    _lib.check(lib.rp_emm_grad_bf16(_p(qkv), ld, _p(xa), _p(wp), _p(rlse2), _p(clse2), _p(rho), _p(gam), _p(dqkv), Z, HEADS, sc, 1, _st()),
-               "rp_emm_grad_bf16(k)")
+        lib.rp_emm_grad_bf16(_p(qkv), ld, _p(xa), _p(w), _p(rlse2), _p(clse2), _p(rho), _p(gam), _p(dqkv), Z, HEADS, sc, 0, _st())
+    lib.rp_emm_grad_bf16(_p(qkv), ld, _p(xa), _p(wp), _p(rlse2), _p(clse2), _p(rho), _p(gam), _p(dqkv), Z, HEADS, sc, 1, _st())
     return dqkv
 
 
@@ -1320,11 +1309,11 @@ class TokensFn(_Fn):
         if nhwc:
             src = feat.permute(0, 2, 3, 1)              # [Z,H,W,C] view, contiguous
             _chk(src, pos_embed)
-            _lib.check(lib.rp_tokens_fwd_nhwc(_p(src), _p(pos_embed), _p(x), Z, C, N, _st()), "rp_tokens_fwd_nhwc")
+            lib.rp_tokens_fwd_nhwc(_p(src), _p(pos_embed), _p(x), Z, C, N, _st())
         else:
             feat = feat.contiguous()
             _chk(feat, pos_embed)
-            _lib.check(lib.rp_tokens_fwd(_p(feat), _p(pos_embed), _p(x), Z, C, N, _st()), "rp_tokens_fwd")
+            lib.rp_tokens_fwd(_p(feat), _p(pos_embed), _p(x), Z, C, N, _st())
         return x
 
     @staticmethod
@@ -1337,7 +1326,7 @@ class TokensFn(_Fn):
             _, _, H, W = ctx.shape
             return dx.view(Z, H, W, C).permute(0, 3, 1, 2), dpe          # channels-last gradient, no copy
         dfeat = _empty(*ctx.shape, like=dx)
-        _lib.check(lib.rp_tokens_bwd(_p(dx), _p(dfeat), Z, C, N, _st()), "rp_tokens_bwd")
+        lib.rp_tokens_bwd(_p(dx), _p(dfeat), Z, C, N, _st())
         return dfeat, dpe
 
 
@@ -1379,9 +1368,8 @@ def mlp_fused(x2d, gamma, beta, w1, b1, w2, b2, eps=LN_EPS, train=False, out_dty
     else:
         w1k, w2k = w1, w2
     with timed("mlp_fused_fwd" + ("" if train else "_eval") + ("_bf16" if bf else ""), 4.0 * M * DIM * Hd, 4.0 * (2 * M * DIM + 2 * DIM * Hd + (M * DIM + 2 * M * Hd if train else 0))):
-        _lib.check(lib.rp_mlp_fused_fwd(_p(x2d), _p(gamma), _p(beta), _p(w1k), _p(b1), _p(w2k), _p(b2), _p(y), _p(ws), M, x2d.shape[1],
-                                        Hd, eps, _p(xn), _p(mean), _p(rstd), _p(h), _p(hpre), 1 if bf else 0, (2 if obf else 0) | (8 if xnbf else 0) | (16 if bf and MLP_W2_CHUNK_MAJOR else 0), _st()),
-                   "rp_mlp_fused_fwd")
+        lib.rp_mlp_fused_fwd(_p(x2d), _p(gamma), _p(beta), _p(w1k), _p(b1), _p(w2k), _p(b2), _p(y), _p(ws), M, x2d.shape[1],
+                             Hd, eps, _p(xn), _p(mean), _p(rstd), _p(h), _p(hpre), 1 if bf else 0, (2 if obf else 0) | (8 if xnbf else 0) | (16 if bf and MLP_W2_CHUNK_MAJOR else 0), _st())
     return (y, xn, mean, rstd, h, hpre) if train else y
 
 
@@ -1466,14 +1454,13 @@ def mlp_fused_bwd(dy, hpre, w1, w2, out_dtype=None, ln=None):
         C = dy.shape[1]
         lnpart = _empty(lib.rp_mlp_fused_bwd_ln_part_rows(M), 3 * C, like=dy)
         with timed("mlp_fused_bwd_ln" + ("_bf16" if bf else ""), 4.0 * M * C * hpre.shape[1], M * (float(hpre.element_size()) * 2 * hpre.shape[1] + 4.0 * 4 * C)):
-            _lib.check(lib.rp_mlp_fused_bwd_ln(_p(dy), _p(hpre), _p(w2t), _p(w1t), _p(dhp), _p(dxn), _p(colpart), _p(ws), M, C,
-                                               hpre.shape[1], 1 if bf else 0, io, _p(x), _p(gamma), _p(mean), _p(rstd), _p(lnpart), _st()),
-                       "rp_mlp_fused_bwd_ln")
+            lib.rp_mlp_fused_bwd_ln(_p(dy), _p(hpre), _p(w2t), _p(w1t), _p(dhp), _p(dxn), _p(colpart), _p(ws), M, C,
+                                    hpre.shape[1], 1 if bf else 0, io, _p(x), _p(gamma), _p(mean), _p(rstd), _p(lnpart), _st())
         sums = colsum(lnpart)
         return dhp, (dxn, sums[:C], sums[C:2 * C], sums[2 * C:]), colpart
     with timed("mlp_fused_bwd" + ("_bf16" if bf else ""), 4.0 * M * dy.shape[1] * hpre.shape[1], M * (float(hpre.element_size()) * 2 * hpre.shape[1] + 4.0 * 2 * dy.shape[1])):
-        _lib.check(lib.rp_mlp_fused_bwd(_p(dy), _p(hpre), _p(w2t), _p(w1t), _p(dhp), _p(dxn), _p(colpart), _p(ws), M, dy.shape[1],
-                                        hpre.shape[1], 1 if bf else 0, io, _st()), "rp_mlp_fused_bwd")
+        lib.rp_mlp_fused_bwd(_p(dy), _p(hpre), _p(w2t), _p(w1t), _p(dhp), _p(dxn), _p(colpart), _p(ws), M, dy.shape[1],
+                             hpre.shape[1], 1 if bf else 0, io, _st())
     return dhp, dxn, colpart
 
 
@@ -1689,7 +1676,7 @@ def _regress_fwd(feats, gs, w0, b0, w2, b2, w4, b4):
     gs = gs.contiguous()
     _chk(gs)
     out = _empty(B, 2, 7, like=feats)
-    _lib.check(lib.rp_pose_normalize_fwd(_p(pred), _p(gs), _p(out), B, _st()), "rp_pose_normalize_fwd")
+    lib.rp_pose_normalize_fwd(_p(pred), _p(gs), _p(out), B, _st())
     return out, h1, h2, pred, w4p
 
 
@@ -1698,7 +1685,7 @@ def _regress_bwd(dout, feats, h1, h2, pred, w0, w2, w4p):
     B = feats.shape[0]
     dout = dout.contiguous()
     dpred = _empty(B, 14, like=dout)
-    _lib.check(lib.rp_pose_normalize_bwd(_p(pred), _p(dout), _p(dpred), B, _st()), "rp_pose_normalize_bwd")
+    lib.rp_pose_normalize_bwd(_p(pred), _p(dout), _p(dpred), B, _st())
     dp16 = torch.nn.functional.pad(dpred, (0, 2)).contiguous()
     dh2 = linear_dx(dp16, w4p, dact=2, aux=h2)
     dw4, db4 = linear_dw(dp16, h2)[:14].contiguous(), colsum(dpred)
@@ -1816,18 +1803,17 @@ class BnActFn(_Fn):
         y = torch.empty_like(xr)
         if training and stats is not None:
             mean, rstd = torch.empty(C, device=x.device), torch.empty(C, device=x.device)
-            _lib.check(lib.rp_bn_stats_from_partials(_p(stats), stats.shape[0], R, C, _p(_zeros(C, xr.device)), _p(mean), _p(rstd),
-                                                     _p(running_mean), _p(running_var), float(momentum), float(eps), _st()),
-                       "rp_bn_stats_from_partials")
+            lib.rp_bn_stats_from_partials(_p(stats), stats.shape[0], R, C, _p(_zeros(C, xr.device)), _p(mean), _p(rstd),
+                                          _p(running_mean), _p(running_var), float(momentum), float(eps), _st())
         elif training:
             mean, rstd = _empty(C, like=xr), _empty(C, like=xr)
             part = torch.empty(lib.rp_bn_partial_blocks(R) * 2 * C, device=x.device, dtype=torch.float64)
-            _lib.check(lib.rp_bn_stats(_p(xr), R, C, _p(part), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
-                                       float(momentum), float(eps), bf, _st()), "rp_bn_stats")
+            lib.rp_bn_stats(_p(xr), R, C, _p(part), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
+                            float(momentum), float(eps), bf, _st())
         else:
             mean, rstd = running_mean, torch.rsqrt(running_var + eps)
-        _lib.check(lib.rp_bn_apply_fwd(_p(xr), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(rr), _p(y), R, C, 1 if relu else 0,
-                                       bf, _st()), "rp_bn_apply_fwd")
+        lib.rp_bn_apply_fwd(_p(xr), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(rr), _p(y), R, C, 1 if relu else 0,
+                            bf, _st())
         global _BN_LAST
         _BN_LAST = None
         if _train(ctx):
@@ -1861,13 +1847,13 @@ class BnActFn(_Fn):
         if hit is not None and hit[0] == dyr.data_ptr() and training and relu and not has_res and not bf:
             # dy IS the masked gradient g, written by the convolution kernel that produced it together with the column sums of g and g * xhat
             part = hit[1]
-            _lib.check(lib.rp_bn_bwd_from_partials(_p(dyr), _p(xr), _p(mean), _p(rstd), _p(gamma), _p(part), part.shape[0], _p(dx), _p(dgamma),
-                                                   _p(dbeta), _p(c12), R, C, _st()), "rp_bn_bwd_from_partials")
+            lib.rp_bn_bwd_from_partials(_p(dyr), _p(xr), _p(mean), _p(rstd), _p(gamma), _p(part), part.shape[0], _p(dx), _p(dgamma),
+                                        _p(dbeta), _p(c12), R, C, _st())
             return (dx.permute(0, 3, 1, 2), dgamma, dbeta, None, None, None, None, None, None, None, None)
         # (a gradient that was masked by a producer but arrives as another tensor takes the full path: masking twice is the identity)
         part = torch.empty(lib.rp_bn_partial_blocks(R) * 2 * C, device=xr.device, dtype=torch.float64)
-        _lib.check(lib.rp_bn_bwd(_p(dyr), _p(y), _p(xr), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dx), _p(dres), _p(dgamma), _p(dbeta),
-                                 _p(part), _p(c12), R, C, 1 if relu else 0, 1 if training else 0, bf, _st()), "rp_bn_bwd")
+        lib.rp_bn_bwd(_p(dyr), _p(y), _p(xr), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dx), _p(dres), _p(dgamma), _p(dbeta),
+                      _p(part), _p(c12), R, C, 1 if relu else 0, 1 if training else 0, bf, _st())
         return (dx.permute(0, 3, 1, 2), dgamma, dbeta, None, None,
                 None if dres is None else dres.permute(0, 3, 1, 2), None, None, None, None, None)
 
@@ -2058,8 +2044,8 @@ def conv3x3_c64_f32(x_nhwc, w_ohwi, input_gradient=False, want_stats=False, res=
     y = torch.empty_like(x_nhwc)
     stats = torch.empty(lib.rp_conv3x3_c64_f32_blocks(N), 2, 64, device=x_nhwc.device, dtype=torch.float64) if want_stats else None
     with timed("conv3x3_c64_f32", 2.0 * N * 56 * 56 * 64 * 64 * 9, 4.0 * N * 56 * 56 * (128 if res is None else 192)):
-        _lib.check(lib.rp_conv3x3_c64_f32(_p(x_nhwc), _p(w_ohwi), _p(y), _p(stats), _p(res), _bn_mask(bn, y, want_stats), N, 56, 56,
-                                          1 if input_gradient else 0, _st()), "rp_conv3x3_c64_f32")
+        lib.rp_conv3x3_c64_f32(_p(x_nhwc), _p(w_ohwi), _p(y), _p(stats), _p(res), _bn_mask(bn, y, want_stats), N, 56, 56,
+                               1 if input_gradient else 0, _st())
     return (y, stats) if want_stats else y
 
 
@@ -2150,8 +2136,8 @@ def conv3x3_c128_f32(x_nhwc, w_ohwi, bias=None, input_gradient=False, want_stats
     stats = (torch.empty(lib.rp_conv3x3_c128_f32_blocks(N, CO) // (CO // 64), 2, CO, device=x_nhwc.device, dtype=torch.float64)
              if want_stats else None)
     with timed("conv3x3_c128_f32", 2.0 * N * 28 * 28 * 128 * CO * 9, 4.0 * N * 28 * 28 * (128 + CO)):
-        _lib.check(lib.rp_conv3x3_c128_f32(_p(x_nhwc), _p(w_ohwi), _p(bias), _p(y), _p(stats), N, 28, 28, CO, 1 if input_gradient else 0,
-                                           _st()), "rp_conv3x3_c128_f32")
+        lib.rp_conv3x3_c128_f32(_p(x_nhwc), _p(w_ohwi), _p(bias), _p(y), _p(stats), N, 28, 28, CO, 1 if input_gradient else 0,
+                                _st())
     return (y, stats) if want_stats else y
 
 
@@ -2323,7 +2309,7 @@ class GeodesicLossFn(_Fn):
         losses = _empty(2, like=Gs)
         dmean = _empty(2, B, 2, 7, like=Gs)
         scratch = _empty(60 * B, like=Gs)
-        _lib.check(lib.rp_geodesic_loss(_p(Ps), _p(Gs), _p(losses), _p(dmean), _p(scratch), B, _st()), "rp_geodesic_loss")
+        lib.rp_geodesic_loss(_p(Ps), _p(Gs), _p(losses), _p(dmean), _p(scratch), B, _st())
         ctx.save_for_backward(dmean)
         return losses[0], losses[1]
 
@@ -2348,7 +2334,7 @@ class MaxPool3x3s2Fn(_Fn):
         OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         y = torch.empty(N, OH, OW, C, device=x.device, dtype=xr.dtype)
         idx = torch.empty(N, OH, OW, C, device=x.device, dtype=torch.uint8)
-        _lib.check(lib.rp_maxpool3x3s2_fwd(_p(xr), _p(y), ctypes.c_void_p(idx.data_ptr()), N, H, W, C, bf, _st()), "rp_maxpool3x3s2_fwd")
+        lib.rp_maxpool3x3s2_fwd(_p(xr), _p(y), ctypes.c_void_p(idx.data_ptr()), N, H, W, C, bf, _st())
         ctx.save_for_backward(idx)
         ctx.shape = (N, C, H, W)
         return y.permute(0, 3, 1, 2)
@@ -2363,7 +2349,7 @@ class MaxPool3x3s2Fn(_Fn):
             dyr = dyr.contiguous()
         bf = _chk_act(dyr)
         dx = torch.empty(N, H, W, C, device=dy.device, dtype=dyr.dtype)
-        _lib.check(lib.rp_maxpool3x3s2_bwd(_p(dyr), ctypes.c_void_p(idx.data_ptr()), _p(dx), N, H, W, C, bf, _st()), "rp_maxpool3x3s2_bwd")
+        lib.rp_maxpool3x3s2_bwd(_p(dyr), ctypes.c_void_p(idx.data_ptr()), _p(dx), N, H, W, C, bf, _st())
         return dx.permute(0, 3, 1, 2)
 
 
@@ -2380,7 +2366,7 @@ def conv_stem_fwd(x_padded_nhwc, w, want_stats=False):
     y = torch.empty(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64, device=w.device, dtype=torch.float32)
     stats = torch.empty(lib.rp_conv_stem_blocks(N, H, W), 2, 64, device=w.device, dtype=torch.float64) if want_stats else None
     with timed("conv_stem_fwd", 2.0 * N * (H // 2) * (W // 2) * 64 * 147, 4.0 * N * (3.0 * H * W + 64.0 * (H // 2) * (W // 2))):
-        _lib.check(lib.rp_conv_stem_fwd(_p(x_padded_nhwc), _p(wr), _p(y), _p(stats), N, H, W, _st()), "rp_conv_stem_fwd")
+        lib.rp_conv_stem_fwd(_p(x_padded_nhwc), _p(wr), _p(y), _p(stats), N, H, W, _st())
     return (y, stats) if want_stats else y
 
 
@@ -2401,7 +2387,7 @@ def conv3x3_c64_bf16(x_nhwc, w, scale=None, shift=None, want_stats=False):
     y = torch.empty_like(x_nhwc)
     stats = torch.empty(lib.rp_conv3x3_c64_blocks(N), 2, 64, device=x_nhwc.device, dtype=torch.float64) if want_stats else None
     with timed("conv3x3_c64_bf16", 2.0 * N * 56 * 56 * 64 * 64 * 9, 2.0 * N * 56 * 56 * 128):
-        _lib.check(lib.rp_conv3x3_c64_bf16(_p(x_nhwc), _p(w), _p(y), _p(scale), _p(shift), _p(stats), N, 56, 56, _st()), "rp_conv3x3_c64_bf16")
+        lib.rp_conv3x3_c64_bf16(_p(x_nhwc), _p(w), _p(y), _p(scale), _p(shift), _p(stats), N, 56, 56, _st())
     return (y, stats) if want_stats else y
 
 
@@ -2417,7 +2403,7 @@ def conv3x3_c64_wgrad_bf16(x_nhwc, dy_nhwc):
     ws = torch.empty(nb // 4, device=x_nhwc.device, dtype=torch.float32)
     dw = torch.empty(64, 3, 3, 64, device=x_nhwc.device, dtype=torch.bfloat16)
     with timed("conv3x3_c64_wgrad_bf16", 2.0 * N * 56 * 56 * 64 * 64 * 9, 2.0 * N * 56 * 56 * 128):
-        _lib.check(lib.rp_conv3x3_c64_wgrad_bf16(_p(x_nhwc), _p(dy_nhwc), _p(dw), _p(ws), nb, N, 56, 56, _st()), "rp_conv3x3_c64_wgrad_bf16")
+        lib.rp_conv3x3_c64_wgrad_bf16(_p(x_nhwc), _p(dy_nhwc), _p(dw), _p(ws), nb, N, 56, 56, _st())
     return dw
 
 
@@ -2433,7 +2419,7 @@ def conv3x3_c64_wgrad_f32(x_nhwc, dy_nhwc):
     ws = torch.empty(nb // 4, device=x_nhwc.device, dtype=torch.float32)
     dw = torch.empty(64, 3, 3, 64, device=x_nhwc.device, dtype=torch.float32)
     with timed("conv3x3_c64_wgrad_f32", 2.0 * N * 56 * 56 * 64 * 64 * 9, 4.0 * N * 56 * 56 * 128):
-        _lib.check(lib.rp_conv3x3_c64_wgrad_f32(_p(x_nhwc), _p(dy_nhwc), _p(dw), _p(ws), nb, N, 56, 56, _st()), "rp_conv3x3_c64_wgrad_f32")
+        lib.rp_conv3x3_c64_wgrad_f32(_p(x_nhwc), _p(dy_nhwc), _p(dw), _p(ws), nb, N, 56, 56, _st())
     return dw
 
 
@@ -2450,7 +2436,7 @@ def conv_stem_fwd_bf16(x_padded_nhwc, w, want_stats=False):
     y = torch.empty(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64, device=w.device, dtype=torch.bfloat16)
     stats = torch.empty(lib.rp_conv_stem_bf16_blocks(N, H, W), 2, 64, device=w.device, dtype=torch.float64) if want_stats else None
     with timed("conv_stem_fwd_bf16", 2.0 * N * (H // 2) * (W // 2) * 64 * 147, N * (4.0 * 3 * H * W + 2.0 * 64 * (H // 2) * (W // 2))):
-        _lib.check(lib.rp_conv_stem_fwd_bf16(_p(x_padded_nhwc), _p(wr), _p(y), _p(stats), N, H, W, _st()), "rp_conv_stem_fwd_bf16")
+        lib.rp_conv_stem_fwd_bf16(_p(x_padded_nhwc), _p(wr), _p(y), _p(stats), N, H, W, _st())
     return (y, stats) if want_stats else y
 
 
@@ -2468,7 +2454,7 @@ def conv_stem_wgrad_bf16(x_padded_nhwc, dy_nhwc):
     ws = torch.empty((nb + 3) // 4, device=dy_nhwc.device, dtype=torch.float32)
     dw = torch.empty(64, 7, 7, 3, device=dy_nhwc.device, dtype=torch.float32)
     with timed("conv_stem_wgrad_bf16", 2.0 * N * 112 * 112 * 64 * 147, N * (4.0 * 3 * 224 * 224 + 2.0 * 64 * 112 * 112)):
-        _lib.check(lib.rp_conv_stem_wgrad_bf16(_p(x_padded_nhwc), _p(dy_nhwc), _p(dw), _p(ws), nb, N, 224, 224, _st()), "rp_conv_stem_wgrad_bf16")
+        lib.rp_conv_stem_wgrad_bf16(_p(x_padded_nhwc), _p(dy_nhwc), _p(dw), _p(ws), nb, N, 224, 224, _st())
     return dw
 
 
@@ -2484,7 +2470,7 @@ def conv_stem_wgrad_f32(x_padded_nhwc, dy_nhwc):
     ws = torch.empty((nb + 3) // 4, device=dy_nhwc.device, dtype=torch.float32)
     dw = torch.empty(64, 7, 7, 3, device=dy_nhwc.device, dtype=torch.float32)
     with timed("conv_stem_wgrad_f32", 2.0 * N * 112 * 112 * 64 * 147, 4.0 * N * (3.0 * 224 * 224 + 64.0 * 112 * 112)):
-        _lib.check(lib.rp_conv_stem_wgrad_f32(_p(x_padded_nhwc), _p(dy_nhwc), _p(dw), _p(ws), nb, N, 224, 224, _st()), "rp_conv_stem_wgrad_f32")
+        lib.rp_conv_stem_wgrad_f32(_p(x_padded_nhwc), _p(dy_nhwc), _p(dw), _p(ws), nb, N, 224, 224, _st())
     return dw
 
 
@@ -2578,21 +2564,20 @@ class BnReluPoolFn(_Fn):
         R = N * H * W
         if training and stats is not None:
             mean, rstd = _empty(C, like=xr), _empty(C, like=xr)
-            _lib.check(lib.rp_bn_stats_from_partials(_p(stats), stats.shape[0], R, C, _p(_zeros(C, xr.device)), _p(mean), _p(rstd),
-                                                     _p(running_mean), _p(running_var), float(momentum), float(eps), _st()),
-                       "rp_bn_stats_from_partials")
+            lib.rp_bn_stats_from_partials(_p(stats), stats.shape[0], R, C, _p(_zeros(C, xr.device)), _p(mean), _p(rstd),
+                                          _p(running_mean), _p(running_var), float(momentum), float(eps), _st())
         elif training:
             mean, rstd = _empty(C, like=xr), _empty(C, like=xr)
             part = torch.empty(lib.rp_bn_partial_blocks(R) * 2 * C, device=x.device, dtype=torch.float64)
-            _lib.check(lib.rp_bn_stats(_p(xr), R, C, _p(part), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
-                                       float(momentum), float(eps), bf, _st()), "rp_bn_stats")
+            lib.rp_bn_stats(_p(xr), R, C, _p(part), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
+                            float(momentum), float(eps), bf, _st())
         else:
             mean, rstd = running_mean, torch.rsqrt(running_var + eps)
         OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         y = torch.empty(N, OH, OW, C, device=x.device, dtype=xr.dtype)
         idx = torch.empty(N, OH, OW, C, device=x.device, dtype=torch.uint8)
-        _lib.check(lib.rp_bn_relu_pool_fwd(_p(xr), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(y), ctypes.c_void_p(idx.data_ptr()),
-                                           N, H, W, C, bf, _st()), "rp_bn_relu_pool_fwd")
+        lib.rp_bn_relu_pool_fwd(_p(xr), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(y), ctypes.c_void_p(idx.data_ptr()),
+                                N, H, W, C, bf, _st())
         if _train(ctx):
             ctx.save_for_backward(xr, idx, mean, rstd, gamma, beta)
             ctx.cfg = (N, C, H, W, bool(training))
@@ -2612,9 +2597,8 @@ class BnReluPoolFn(_Fn):
         dx = torch.empty_like(xr)
         dgamma, dbeta, c12 = _empty(C, like=xr), _empty(C, like=xr), _empty(2 * C, like=xr)
         part = torch.empty(lib.rp_bn_partial_blocks(N * H * W) * 2 * C, device=xr.device, dtype=torch.float64)
-        _lib.check(lib.rp_bn_relu_pool_bwd(_p(dyr), ctypes.c_void_p(idx.data_ptr()), _p(xr), _p(mean), _p(rstd), _p(gamma), _p(beta),
-                                           _p(dx), _p(dgamma), _p(dbeta), _p(part), _p(c12), N, H, W, C, 1 if training else 0, bf, _st()),
-                   "rp_bn_relu_pool_bwd")
+        lib.rp_bn_relu_pool_bwd(_p(dyr), ctypes.c_void_p(idx.data_ptr()), _p(xr), _p(mean), _p(rstd), _p(gamma), _p(beta),
+                                _p(dx), _p(dgamma), _p(dbeta), _p(part), _p(c12), N, H, W, C, 1 if training else 0, bf, _st())
         return dx.permute(0, 3, 1, 2), dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -2658,5 +2642,5 @@ def augment_pairs(images_u8, params, out_h, out_w):
         raise ValueError("augment_pairs params must be [B,9]")
     out = torch.empty(B, 2, 3, out_h, out_w, device=images_u8.device, dtype=torch.float32)
     ws = torch.empty(B * lib.rp_augment_blocks(), device=images_u8.device, dtype=torch.float64)
-    _lib.check(lib.rp_augment_pairs(_p(images_u8), _p(params), _p(out), _p(ws), B, H, W, out_h, out_w, _st()), "rp_augment_pairs")
+    lib.rp_augment_pairs(_p(images_u8), _p(params), _p(out), _p(ws), B, H, W, out_h, out_w, _st())
     return out

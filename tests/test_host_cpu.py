@@ -38,6 +38,136 @@ def test_library_exports_every_declared_symbol():
     assert typed.rp_layernorm_bwd_blocks(73728) == 1152 and typed.rp_layernorm_bwd_blocks(100) == 2
 
 
+PARSER_FORMS = """
+/* every form the real header uses, once; a comment with a prototype rp_fake(int x); and a ; in it */
+#ifndef FORMS_H
+#define FORMS_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define RP_OK 0
+#define RP_EBADSHAPE (-1)
+#define RP_TASK_MAX 8
+typedef struct RpTask {
+  const float* in; /* keyword; with a semicolon */
+  int rows, cols, ld;
+  long long stride;
+  size_t bytes;
+  float scale;
+  void* ev;
+} RpTask;
+const char* rp_name(void);
+void* rp_make(void);
+void rp_drop(void* ev);
+float rp_ms(void* start, void* stop);
+size_t rp_bytes(const RpTask* tasks, int n, size_t have);
+int rp_blocks(long long R);
+int rp_run(const RpTask* t, const void* x, unsigned char* idx, const unsigned char* idx2, double* part,
+           int* count, float eps,
+           long long R, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif /* FORMS_H */
+"""
+
+
+def test_header_parser_forms():
+    from ctypes import POINTER, c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p, sizeof
+    from rel_pose_amd import _lib
+    consts, structs, sigs, status = _lib._header_contract(PARSER_FORMS)
+    assert consts == {"RP_OK": 0, "RP_EBADSHAPE": -1, "RP_TASK_MAX": 8}
+    assert list(structs) == ["RpTask"]
+    T = structs["RpTask"]
+    assert T._fields_ == [("in_", c_void_p), ("rows", c_int), ("cols", c_int), ("ld", c_int), ("stride", c_longlong),
+                          ("bytes", c_size_t), ("scale", c_float), ("ev", c_void_p)]
+    assert sizeof(T) == 56 and T.stride.offset == 24
+    P = c_void_p
+    assert list(sigs.items()) == [
+        ("rp_name", (c_char_p, [])),
+        ("rp_make", (c_void_p, [])),
+        ("rp_drop", (None, [P])),
+        ("rp_ms", (c_float, [P, P])),
+        ("rp_bytes", (c_size_t, [POINTER(T), c_int, c_size_t])),
+        ("rp_blocks", (c_int, [c_longlong])),
+        ("rp_run", (c_int, [POINTER(T), P, P, P, P, P, c_float, c_longlong, P])),
+    ]
+    assert status == {"rp_run"}
+
+
+@pytest.mark.parametrize("old, new", [
+    ("int rp_blocks(long long R);", "int rp_blocks(short x);"),                       # a type the header does not use
+    ("int rp_blocks(long long R);", "short rp_blocks(long long R);"),
+    ("int rp_blocks(long long R);", "int rp_blocks(int (*cb)(int));"),                # function pointer
+    ("  float scale;", "  float scale[4];"),                                          # array field
+    ("  float scale;", "  short scale;"),
+    ("  float scale;", "  float *a, *b;"),
+    ("#define RP_TASK_MAX 8", "#define RP_TASK_MAX (4 + 4)"),                         # a macro form it does not evaluate
+    ("#define RP_TASK_MAX 8", "#define RP_MIN(a, b) ((a) < (b) ? (a) : (b))"),
+    ("void rp_drop(void* ev);", "void rp_drop(void* ev, void* stream);"),             # a launch must return a status
+    ("void rp_drop(void* ev);", "void rp_drop(void* ev) { }"),                        # anything that is not a declaration
+    ("void rp_drop(void* ev);", "void rp_drop(void* ev);\nint rp_blocks(int R);"),    # declared twice
+])
+def test_header_parser_is_strict(old, new):
+    from rel_pose_amd import _lib
+    assert old in PARSER_FORMS
+    with pytest.raises(ValueError) as e:
+        _lib._header_contract(PARSER_FORMS.replace(old, new))
+    assert "relpose_hip.h" in str(e.value)
+
+
+def test_binding_matches_the_hand_written_one_it_replaced():
+    # sizes, offsets and signatures of the ctypes.Structure classes / type lists that rel_pose_amd/_lib.py spelled out before it
+    # read them from the header (ABI 26)
+    from ctypes import POINTER, c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p, sizeof
+    from rel_pose_amd import _lib
+    assert [sizeof(s) for s in (_lib.RpGemm, _lib.RpColsumTask, _lib.RpBnMask, _lib.RpSplitkTask, _lib.RpTransposeTask)] == \
+        [232, 32, 40, 40, 24]
+    assert (_lib.RpGemm.stride_a.offset, _lib.RpGemm.workspace_bytes.offset, _lib.RpGemm.defer_reduce.offset) == (64, 104, 228)
+    assert _lib.RpColsumTask.out.offset == 24 and _lib.RpSplitkTask.trans_c.offset == 32
+    assert [n for n, _ in _lib.RpColsumTask._fields_] == ["in_", "rows", "cols", "ld", "out"]
+    assert (_lib.RP_COLSUM_MAX, _lib.RP_SPLITK_MAX, _lib.RP_TRANSPOSE_MAX) == (8, 8, 24)
+    assert _lib.RP_ERRORS == {-1: "bad shape", -2: "misaligned pointer/stride", -3: "workspace too small", -4: "unsupported"}
+    P, I, F, L = c_void_p, c_int, c_float, c_longlong
+    lib = _lib.load()
+    for name, (res, args) in {
+        "rp_target_arch": (c_char_p, []),
+        "rp_event_destroy": (None, [P]),
+        "rp_gemm": (c_int, [POINTER(_lib.RpGemm), P]),
+        "rp_bn_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, P]),
+        "rp_conv3x3_c64_f32": (c_int, [P, P, P, P, P, POINTER(_lib.RpBnMask), I, I, I, I, P]),
+        "rp_mlp_fused_fwd": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, F, P, P, P, P, P, I, I, P]),
+    }.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    assert lib.rp_colsum.argtypes[6] is c_size_t and lib.rp_gemm_workspace_bytes.restype is c_size_t
+
+
+def test_status_is_checked_where_work_is_launched_and_nowhere_else():
+    from ctypes import c_int
+    from rel_pose_amd import _lib
+    header = open(os.path.join(ROOT, "include", "relpose_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    launches = set(re.findall(r"\b(rp_[a-z0-9_]+)\s*\([^()]*\bvoid\s*\*\s*stream\s*\)", header))
+    lib = _lib.load()
+    hooked = {n for n in _lib.EXPORTS if getattr(lib, n).errcheck is not None}
+    assert hooked == launches and len(launches) == 76
+    assert all(getattr(lib, n).restype is c_int for n in hooked)
+    counts = {n for n in _lib.EXPORTS if getattr(lib, n).restype is c_int} - hooked
+    assert len(counts) == 18 and {"rp_abi_version", "rp_abi_export_count", "rp_bn_partial_blocks", "rp_dw192_f32_splits",
+                                  "rp_linear_rows192_tile_rows", "rp_mlp_fused_bwd_ln_part_rows"} <= counts
+    assert all(n.endswith(("_blocks", "_splits", "_tile_rows", "_part_rows")) for n in counts - {"rp_abi_version", "rp_abi_export_count"})
+    assert not {n for n in hooked if n.startswith("rp_event_") or n.endswith("_workspace_bytes")}
+    hook = lib.rp_gemm.errcheck
+    fn = types.SimpleNamespace(__name__="rp_stand_in")
+    assert hook(0, fn, ()) == 0
+    with pytest.raises(RuntimeError, match=r"rel_pose_amd: rp_stand_in failed: bad shape \(RP error -1\)"):
+        hook(-1, fn, ())
+    with pytest.raises(RuntimeError, match=r"rel_pose_amd: rp_stand_in failed: hipError 98"):
+        hook(98, fn, ())
+
+
 def test_state_dict_contract_and_dropin_alias():
     from rel_pose_amd.model import ViTEss
     from src.model import ViTEss as Alias
