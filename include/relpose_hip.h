@@ -14,6 +14,13 @@
  *   - return value: 0 = ok, <0 = RP_E* argument error, >0 = hipError_t from the launch.
  *   - all tensors are fp32, row-major; "ld*" = row stride in floats.
  *   - token count per image is 576 (24x24), head dim 64 (reference src/model.py:19-23).
+ *   - memory contract (tests/test_gpu_memory_contract.py): a call writes EVERY element of the extent documented for each output --
+ *     all rows of per-tile / per-workgroup partial arrays included, ragged last tiles too -- and nothing else: with a row stride larger
+ *     than the width the gap columns are neither read for their value nor written, and an entry point that owns one column block of a
+ *     shared array (the q, k or v third of dqkv) leaves the other blocks alone.  `const` operands are not modified.  No result depends
+ *     on what an output or a workspace held before the call (no atomics, no accumulation into outputs); a workspace's contents after the
+ *     call are unspecified.  A *_workspace_bytes / *_blocks function reports exactly what the call needs; entry points that take
+ *     workspace_bytes refuse less with RP_EWORKSPACE before anything is launched.
  */
 #ifndef RELPOSE_HIP_H
 #define RELPOSE_HIP_H
@@ -84,13 +91,14 @@ typedef struct RpGemm {
   float* colsum_part; /* optional: [2*ceil(M/(64*TM))][N] floats; row (2*mt + wave row) receives the column sums of the FINAL
                        * values that tile stored over its 32*TM rows -- one small rp_colsum over it yields sum_m C[m][n] (the bias
                        * gradient when C is a pre-activation gradient) without re-reading C.  split_k = batch = 1, N % 4 == 0,
-                       * not the [K,M]x[K,N] layout, and the tile must be TN <= 2 (true whenever aux / residual is given). */
+                       * not the [K,M]x[K,N] layout, and the tile must be TN <= 2 (true whenever aux / residual is given).  Every one of
+                       * the 2*ceil(M/(64*TM)) rows is written: a wave row past M receives zeros. */
   /* LayerNorm backward fused into the epilogue (all NULL = off).  With ln_x set, the product op(A) op(B) is taken as the
    * gradient of a LayerNorm OUTPUT (eps / affine as rp_layernorm_fwd) and C receives the gradient of the LayerNorm INPUT:
    *   xhat = (ln_x - ln_mean) * ln_rstd ;  g = P * ln_gamma ;  C = ln_rstd * (g - mean_n(g) - xhat * mean_n(g * xhat)) + residual
    * ln_part [ceil(M/64)][np*192] (np = 3 with a residual, else 2) receives per-64-row-tile column sums of
    * P * xhat (-> d gamma), P (-> d beta) and residual (-> the bias gradient of the Linear that produced that branch); one
-   * rp_colsum over it finishes them.  Requirements: N == 192 == ldc, ln_x / residual contiguous [M,192], no bias / act / aux,
+   * rp_colsum over it finishes them (all ceil(M/64) rows exist; the ragged last tile sums its live rows only).  Requirements: N == 192 == ldc, ln_x / residual contiguous [M,192], no bias / act / aux,
    * split_k = batch = 1 (any operand precision: the epilogue arithmetic is fp32).  Replaces reference autograd of vision_transformer.py:352-353 (LayerNorm backward). */
   const float* ln_x;
   const float* ln_mean;
@@ -298,7 +306,8 @@ int rp_layernorm_bwd_blocks(int rows);
 int rp_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                      const float* add, float* dx, float* dgamma_part, float* dbeta_part, int rows, int C, void* stream);
 
-/* out[c] = sum_r in[r][c]  (two-stage, fixed order).  workspace: rp_colsum_workspace_bytes(rows, cols). */
+/* out[c] = sum_r in[r][c]  (two-stage, fixed order).  workspace: rp_colsum_workspace_bytes(rows, cols) -- 0 when the rows fit one
+ * stage: the workspace arguments are then ignored.  ld >= cols: columns cols..ld-1 of `in` are not read. */
 size_t rp_colsum_workspace_bytes(int rows, int cols);
 int rp_colsum(const float* in, int rows, int cols, int ld, float* out, float* workspace, size_t workspace_bytes, void* stream);
 /* up to RP_COLSUM_MAX independent column sums in ONE stage-1 and ONE stage-2 launch (same arithmetic and order per task as
@@ -316,7 +325,8 @@ int rp_colsum_multi(const RpColsumTask* tasks, int n, float* workspace, size_t w
 /* Image preprocessing (reference src/model.py:115-118,124-125; bit-exact): BGR->RGB, /255, ImageNet mean/std, nearest
  * resize to 224x224.  images [Z,3,H,W] fp32 0..255 -> out: channels-last memory [Z,224,224,3] of a [Z,3,224,224] tensor. */
 int rp_preprocess(const float* images, float* out, int Z, int H, int W, void* stream);
-/* same, written inside a `pad`-pixel zero frame: out [Z, 224 + 2 pad, 224 + 2 pad, 3] (pad = 3: the input rp_conv_stem_fwd takes) */
+/* same, written inside a `pad`-pixel zero frame: out [Z, 224 + 2 pad, 224 + 2 pad, 3] (pad = 3: the input rp_conv_stem_fwd takes); the
+ * frame is part of the output: the kernel writes its zeros on every call */
 int rp_preprocess_padded(const float* images, float* out, int Z, int H, int W, int pad, void* stream);
 
 /* Token layout + learned position embedding: x[z][n][c] = feat[z][c][n] + pos_embed[n][c]
@@ -440,6 +450,9 @@ int rp_posenc(const float* intrinsics, const float* lin24, float* pos, int B, in
  * rp_emm_build_x: gathers v from qkv (col 384 + h*64) and pos[z/2] into x[z][h][576][96].
  * rp_emm_apply : T (optional store, [Z][H][576][96]) and per-workgroup partial F ([Z][H][6][96][96]).
  *                swap != 0 exchanges the roles of q and k / rlse and clse (gives A^T X: used by the backward).
+ *                All 96 columns of T and all 6 x 96 x 96 elements of the partials are written; columns 70..95 of T and rows / columns
+ *                70..95 of F are the products with X's zero padding, i.e. exactly zero as long as x (and x_left) keep columns 70..95 zero
+ *                -- which rp_emm_build_x writes on every call.
  * rp_emm_finalize: g[z^1][c][h*70+a] = sum_wg Fpart[z][h][wg][a][c], zero-padded to ldg (=224) columns
  *                (the reshape/transpose of vision_transformer.py:229-230 plus the output flip of :238).
  */
@@ -453,7 +466,7 @@ int rp_emm_apply(const float* qkv, int ldqkv, const float* x, const float* x_lef
                  const float* s_in, float* t_out, float* f_part, int Z, int H, float scale, int swap, int single, int bf16,
                  void* stream);
 int rp_emm_finalize(const float* f_part, float* g, int Z, int H, int ldg, void* stream);
-int rp_emm_finalize_bwd(const float* dg, float* df, int Z, int H, int ldg, void* stream); /* df[z][h][96][96] */
+int rp_emm_finalize_bwd(const float* dg, float* df, int Z, int H, int ldg, void* stream); /* df[z][h][96][96]: [a][c] = dg[z^1][c][h*70+a] for a, c < 70, zero elsewhere (all 96 x 96 written) */
 /* rowdot: out[r] = sum_c a[r][c]*b[r][c], C = 96 */
 int rp_rowdot96(const float* a, const float* b, float* out, long long rows, void* stream);
 /* EMM gradient pass: owner side o (rows i if swap==0, cols j if swap!=0):

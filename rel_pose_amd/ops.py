@@ -1354,7 +1354,7 @@ def mlp_fused(x2d, gamma, beta, w1, b1, w2, b2, eps=LN_EPS, train=False, out_dty
     key = (x2d.device, M, torch.cuda.current_stream(x2d.device).cuda_stream)
     ws = _mlp_ws.get(key)
     if ws is None:
-        ws = _mlp_ws[key] = torch.empty(max(1, lib.rp_mlp_fused_workspace_bytes(M)) // 4 + 1, device=x2d.device, dtype=torch.float32)
+        ws = _mlp_ws[key] = torch.empty(max(lib.rp_mlp_fused_workspace_bytes(M) // 4, 1), device=x2d.device, dtype=torch.float32)
     Hd = w1.shape[0]
     xn = mean = rstd = h = hpre = None
     xnbf = xn_dtype == torch.bfloat16 and bf and train
@@ -1447,7 +1447,7 @@ def mlp_fused_bwd(dy, hpre, w1, w2, out_dtype=None, ln=None):
     key = (dy.device, M, "bwd", torch.cuda.current_stream(dy.device).cuda_stream)
     ws = _mlp_ws.get(key)
     if ws is None:
-        ws = _mlp_ws[key] = torch.empty(max(1, lib.rp_mlp_fused_bwd_workspace_bytes(M)) // 4 + 1, device=dy.device, dtype=torch.float32)
+        ws = _mlp_ws[key] = torch.empty(max(lib.rp_mlp_fused_bwd_workspace_bytes(M) // 4, 1), device=dy.device, dtype=torch.float32)
     if ln is not None:
         x, gamma, mean, rstd = ln
         _chk(x, gamma, mean, rstd)

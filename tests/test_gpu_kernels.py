@@ -4,6 +4,12 @@ References: (i) the CPU oracle (oracle/relpose_oracle.py, pinned against the rea
 tests/test_oracle_golden.py) evaluated in fp64; (ii) for op-level checks at larger sizes, the same op written
 in plain PyTorch fp64 on the GPU.  Tolerances are stated per test; index/layout ops are bit-exact.
 Measured errors are appended to gpurun_out/test_report.txt.
+
+These tests check VALUES.  Where a kernel writes, that it writes all of its output, and that it does not depend on what its output
+held before (guard bands, poisoned outputs, strided layouts) is the memory contract: tests/test_gpu_memory_contract.py over the
+case table of tests/_contract_cases.py.  (The attention launchers read their RP_ATTN_FWD / RP_ATTN_NW overrides once per process, so
+test_attention_fwd_bwd[2] only selects the two-wave workgroups when it is the first attention launch of the process; the two-wave
+forms are reached by size in test_attention_stored_p_fwd_bwd[30], the full-size tests and the Z = 20 cases of the contract table.)
 """
 import math
 import os

@@ -639,3 +639,30 @@ def test_batched_parameter_cast_passes_gradients_through():
         assert getattr(conv, "_rp_bf16", None) is None          # precision 0: nothing is prepared, conv2d runs the module itself
         y = ops.conv2d(conv, torch.randn(1, 3, 8, 8))
     assert y.dtype == torch.float32 and y.shape == (1, 4, 6, 6)
+
+
+MEMORY_CONTRACT_MAY_SKIP = {
+    "rp_conv_stem_fwd_bf16", "rp_conv_stem_wgrad_bf16", "rp_conv3x3_c64_bf16", "rp_conv3x3_c64_wgrad_bf16", "rp_attn_fwd_bf16",
+    "rp_attn_bwd_delta_bf16", "rp_attn_bwd_bf16", "rp_dw192_bf16", "rp_dw192_split3", "rp_dx_lnbwd_bf16", "rp_emm_build_x_bf16",
+    "rp_emm_apply_bf16", "rp_emm_f_bf16", "rp_emm_w_bf16", "rp_emm_dx_bf16", "rp_emm_grad_bf16"}
+
+
+def test_every_launching_entry_point_has_a_memory_contract_case():
+    """tests/_contract_cases.py (run on the GPU by tests/test_gpu_memory_contract.py) must name every entry point of the header that
+    launches work: a case, or -- only for the bf16 data path and the opt-in split3 kernel -- a reason why not.  A new entry point fails
+    here until it gets a case.  Importing the table initialises neither CUDA nor the library."""
+    import subprocess
+    import sys
+    from rel_pose_amd import _lib
+    from tests import _contract_cases as CC
+    assert set(CC.CASES) | set(CC.UNCOVERED) == set(_lib._STATUS)
+    assert not set(CC.CASES) & set(CC.UNCOVERED)
+    assert set(CC.UNCOVERED) <= MEMORY_CONTRACT_MAY_SKIP
+    assert all(isinstance(r, str) and r.strip() for r in CC.UNCOVERED.values())
+    assert all(CC.CASES[n] and all(callable(b) and b.entry == n and b.ident for b in CC.CASES[n]) for n in CC.CASES)
+    ids = [(b.entry, b.ident) for bs in CC.CASES.values() for b in bs]
+    assert len(ids) == len(set(ids))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", "import torch, tests._contract_cases as c; c.CASES['rp_gemm'][0](); "
+                        "assert not torch.cuda.is_initialized()"], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
