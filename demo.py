@@ -94,6 +94,8 @@ def main(argv=None):
     ap.add_argument("--fc_hidden_size", type=int, default=512)
     ap.add_argument("--pool_size", type=int, default=60)
     ap.add_argument("--transformer_depth", type=int, default=6)
+    ap.add_argument("--matches", metavar="OUT.npz", default="",
+                    help="also write the token correspondences the Essential Matrix Module formed (rel_pose_amd/readout.py)")
     args = ap.parse_args(argv)
     args.fusion_transformer = True
     args.noess = "1" if args.noess else ""
@@ -120,7 +122,25 @@ def main(argv=None):
     else:
         print("predicted R, as quaternion in format qx,qy,qz,qw")
         print(preds[3:])
+    if args.matches:
+        write_matches(model, images, args.matches)
     return preds
+
+
+def write_matches(model, images, path):
+    """--matches: the readout of the pair's EMM attention as an .npz -- row_idx / col_idx [2,3,576], row_stat / col_stat [2,3,576,4],
+    mutual [2,3,576] (rel_pose_amd.readout.Correspondences) and, per head h, match_xy0_h<h> / match_xy1_h<h> [M,2] / match_conf_h<h> [M]:
+    pixel centres (of the images as the model saw them) in image 0 / image 1 of the mutual matches of image 1's attention."""
+    from rel_pose_amd import readout
+    corr = model.correspondences(images)
+    out = {k: getattr(corr, k).cpu().numpy() for k in ("row_idx", "row_stat", "col_idx", "col_stat", "mutual")}
+    counts = []
+    for h in range(corr.row_idx.shape[1]):
+        xy0, xy1, conf = readout.matches_xy(corr, 1, h, images.shape[-2:])
+        out["match_xy0_h%d" % h], out["match_xy1_h%d" % h], out["match_conf_h%d" % h] = xy0.cpu().numpy(), xy1.cpu().numpy(), conf.cpu().numpy()
+        counts.append(int(xy0.shape[0]))
+    np.savez(path, **out)
+    print("mutual matches per head: %s -> %s" % (" ".join(str(c) for c in counts), path))
 
 
 if __name__ == "__main__":

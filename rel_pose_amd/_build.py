@@ -1,5 +1,5 @@
-"""Build librelpose_hip.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or the load
-fails, every op in rel_pose_amd raises."""
+"""Build librelpose_hip.so and librelpose_readout.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
 import sys
@@ -8,6 +8,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librelpose_hip.so")
 SOURCES = ["gemm.hip", "gemm_dma.hip", "rowwise.hip", "attention.hip", "attention_bf16.hip", "dw192_bf16.hip", "dw192_f32.hip", "dw192_split3.hip", "dx_lnbwd_bf16.hip", "emm.hip", "emm_bf16.hip", "batchnorm.hip", "se3loss.hip", "geom.hip", "augment.hip", "mlp_fused.hip", "linear_rows.hip", "conv_stem.hip", "conv_stem_bf16.hip", "conv_stem_wgrad_bf16.hip", "conv_stem_wgrad_f32.hip", "conv3x3_bf16.hip", "conv3x3_wgrad_bf16.hip", "conv3x3_wgrad_f32.hip", "conv3x3_f32.hip", "conv3x3_c128_f32.hip"]
+# the readout library (include/relpose_readout.h): its own sources, outside csrc/ -- the hot path's source set stays what it was
+READOUT_CSRC = os.path.join(HERE, "csrc_readout")
+READOUT_LIB = os.path.join(HERE, "librelpose_readout.so")
+READOUT_SOURCES = ["emm_readout.hip"]
 ARCH = "gfx950"
 
 
@@ -18,24 +22,34 @@ def _hipcc():
     return "hipcc"
 
 
-def needs_build():
-    if not os.path.exists(LIB):
+def _stale(lib, csrc, sources, headers):
+    if not os.path.exists(lib):
         return True
-    t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + _headers()
-    return any(os.path.getmtime(d) > t for d in deps)
+    t = os.path.getmtime(lib)
+    return any(os.path.getmtime(d) > t for d in [os.path.join(csrc, s) for s in sources] + headers)
+
+
+def needs_build():
+    return _stale(LIB, CSRC, SOURCES, _headers())
+
+
+def readout_needs_build():
+    return _stale(READOUT_LIB, READOUT_CSRC, READOUT_SOURCES, _readout_headers())
 
 
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
-    once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file."""
+    once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
+    Both libraries are built under the one lock, each only if it is stale (force: both, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            if not force and not needs_build():      # another rank built it while this one waited
-                return LIB
-            return _build_locked(verbose, force)
+            if force or needs_build():               # (not stale any more: another rank built it while this one waited)
+                _build_locked(verbose, force, LIB, CSRC, SOURCES, _headers())
+            if force or readout_needs_build():
+                _build_locked(verbose, force, READOUT_LIB, READOUT_CSRC, READOUT_SOURCES, _readout_headers())
+            return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
 
@@ -45,18 +59,22 @@ def _headers():
            [os.path.join(os.path.dirname(HERE), "include", "relpose_hip.h")]
 
 
-def _build_locked(verbose, force=False):
+def _readout_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_readout.h")]
+
+
+def _build_locked(verbose, force, lib, csrc, sources, headers):
     """force: every translation unit is recompiled; otherwise only objects older than their source or any header."""
     cc = _hipcc()
     objs = []
     procs = []
-    hdr_t = max(os.path.getmtime(h) for h in _headers())
-    for s in SOURCES:
-        o = os.path.join(CSRC, s.replace(".hip", ".o"))
+    hdr_t = max(os.path.getmtime(h) for h in headers)
+    for s in sources:
+        o = os.path.join(csrc, s.replace(".hip", ".o"))
         objs.append(o)
-        if not force and os.path.exists(o) and os.path.getmtime(o) > max(hdr_t, os.path.getmtime(os.path.join(CSRC, s))):
+        if not force and os.path.exists(o) and os.path.getmtime(o) > max(hdr_t, os.path.getmtime(os.path.join(csrc, s))):
             continue
-        cmd = [cc, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(CSRC, s), "-o", o]
+        cmd = [cc, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(csrc, s), "-o", o]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
@@ -65,13 +83,13 @@ def _build_locked(verbose, force=False):
         if p.returncode != 0:
             sys.stderr.write(out.decode())
             raise RuntimeError("hipcc failed on " + s)
-    tmp = LIB + ".tmp.%d" % os.getpid()
+    tmp = lib + ".tmp.%d" % os.getpid()
     cmd = [cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    os.replace(tmp, LIB)
-    return LIB
+    os.replace(tmp, lib)
+    return lib
 
 
 if __name__ == "__main__":

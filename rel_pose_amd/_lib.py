@@ -29,11 +29,11 @@ _ITEM = re.compile(r"\s*(?:typedef\s+struct\s+(\w+)\s*\{([^{}]*);\s*\}\s*(\w+)\s
                    r'|extern\s+"C"\s*\{|\})')
 
 
-def _declaration(text, structs):
+def _declaration(text, structs, header="relpose_hip.h"):
     """(ctypes type, [names]) of `type name`, `type a, b, c` or a bare `type`, as the header writes them."""
     m = _DECL.fullmatch(text.strip())
     if not m:
-        raise ValueError("relpose_hip.h: cannot parse declaration %r" % text.strip())
+        raise ValueError("%s: cannot parse declaration %r" % (header, text.strip()))
     const, base, star, names = m.groups()
     base, names = " ".join(base.split()), re.split(r"\s*,\s*", names) if names else []
     if star and base in structs and len(names) <= 1:
@@ -42,11 +42,11 @@ def _declaration(text, structs):
         return c_void_p, names
     if not star and not const and base in _SCALARS:
         return _SCALARS[base], names
-    raise ValueError("relpose_hip.h: unknown type in %r" % text.strip())
+    raise ValueError("%s: unknown type in %r" % (header, text.strip()))
 
 
-def _header_contract(text):
-    """(RP_* constants, structures, prototypes, status names) read from the text of include/relpose_hip.h -- the single definition
+def _header_contract(text, header="relpose_hip.h"):
+    """(RP_* constants, structures, prototypes, status names) read from the text of include/<header> -- the single definition
     the library is compiled against and this binding is made from.  prototypes: name -> (restype, argtypes), in header order;
     status names: the entry points whose last parameter is `void* stream` -- they enqueue work and return 0 / RP_E* / hipError_t,
     every other int is a count.  Anything the header does not use today (arrays, function pointers, other types) raises."""
@@ -58,34 +58,34 @@ def _header_contract(text):
             if m:
                 consts[m.group(1)] = int(m.group(2).strip("()"))
             elif re.match(r"\s*#\s*define\s+RP_", line):
-                raise ValueError("relpose_hip.h: cannot parse %r" % line.strip())
+                raise ValueError("%s: cannot parse %r" % (header, line.strip()))
             lines[i] = ""
     code, pos = "\n".join(lines).rstrip(), 0
     while pos < len(code):
         m = _ITEM.match(code, pos)
         if not m:
-            raise ValueError("relpose_hip.h: cannot parse %r" % code[pos:].strip()[:80])
+            raise ValueError("%s: cannot parse %r" % (header, code[pos:].strip()[:80]))
         pos = m.end()
         tag, body, alias, ret, name, params = m.groups()
         if tag:
             if tag != alias or tag in structs:
-                raise ValueError("relpose_hip.h: cannot parse struct %s" % tag)
+                raise ValueError("%s: cannot parse struct %s" % (header, tag))
             fields = []
             for decl in body.split(";"):
-                ctype, names = _declaration(decl, structs)
+                ctype, names = _declaration(decl, structs, header)
                 if not names:
-                    raise ValueError("relpose_hip.h: field without a name in struct %s: %r" % (tag, decl.strip()))
+                    raise ValueError("%s: field without a name in struct %s: %r" % (header, tag, decl.strip()))
                 fields += [(n + "_" if keyword.iskeyword(n) else n, ctype) for n in names]
             structs[tag] = type(tag, (Structure,), {"_fields_": fields})
         elif name:
             ret, params = " ".join(ret.split()), [p.strip() for p in params.split(",")]
-            args = [] if params == ["void"] else [_declaration(p, structs) for p in params]
+            args = [] if params == ["void"] else [_declaration(p, structs, header) for p in params]
             if name in sigs or any(len(names) != 1 for _, names in args):
-                raise ValueError("relpose_hip.h: cannot parse prototype of %s" % name)
-            res = None if ret == "void" else c_char_p if ret == "const char*" else _declaration(ret, structs)[0]
+                raise ValueError("%s: cannot parse prototype of %s" % (header, name))
+            res = None if ret == "void" else c_char_p if ret == "const char*" else _declaration(ret, structs, header)[0]
             if re.fullmatch(r"void\s*\*\s*stream", params[-1]):
                 if res is not c_int:
-                    raise ValueError("relpose_hip.h: %s takes a stream but does not return int" % name)
+                    raise ValueError("%s: %s takes a stream but does not return int" % (header, name))
                 status.add(name)
             sigs[name] = (res, [ctype for ctype, _ in args])
     return consts, structs, sigs, status
@@ -102,6 +102,15 @@ RpGemm, RpColsumTask, RpBnMask, RpSplitkTask, RpTransposeTask = (
     _STRUCTS[n] for n in ("RpGemm", "RpColsumTask", "RpBnMask", "RpSplitkTask", "RpTransposeTask"))
 EXPORTS = tuple(_PROTOTYPES)
 DECLARED = set(EXPORTS)
+
+
+# the readout library (include/relpose_readout.h -> librelpose_readout.so): the same parser, the same errcheck, the RP_E* codes above
+_READOUT_LIB = None
+READOUT_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_readout.h")
+with open(READOUT_HEADER) as _f:
+    _READOUT_CONSTS, _, _READOUT_PROTOTYPES, _READOUT_STATUS = _header_contract(_f.read(), "relpose_readout.h")
+READOUT_ABI_VERSION = _READOUT_CONSTS["RP_READOUT_ABI_VERSION"]
+READOUT_EXPORTS = tuple(_READOUT_PROTOTYPES)
 
 
 def lib_path():
@@ -137,6 +146,32 @@ def load():
         if name in _STATUS:
             fn.errcheck = _raise_on_status
     _LIB = lib
+    return lib
+
+
+def load_readout():
+    """Load (building if absent or stale) and type librelpose_readout.so.  Raises on any failure: there is no fallback."""
+    global _READOUT_LIB
+    if _READOUT_LIB is not None:
+        return _READOUT_LIB
+    path = _build.READOUT_LIB
+    if _build.readout_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_readout_abi_version.restype = c_int
+    if lib.rp_readout_abi_version() != READOUT_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_readout_abi_version(), READOUT_ABI_VERSION))
+    for name, (res, args) in _READOUT_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _READOUT_STATUS:
+            fn.errcheck = _raise_on_status
+    _READOUT_LIB = lib
     return lib
 
 
