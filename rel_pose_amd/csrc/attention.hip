@@ -14,28 +14,11 @@
 // i.e. the score accumulators feed the second MFMA directly as its B operand (register r of half-wave hi is
 // key acc_row(r,hi)), no LDS round trip, no cross-lane traffic except one xor-32 shuffle for the row max.
 // fp32 v_mfma_f32_32x32x2_f32 throughout: 64 MFMAs (4096 cycles) per 32x32 tile pair, exact fp32 products.
-#include "common.h"
+#include "tile32.h"
 #include "../../include/relpose_hip.h"
 #include <stdlib.h>
-#include <type_traits>
 
 namespace {
-
-template <int OFF> RP_DEV float lds_rd32(unsigned addr) {      // ds_read_b32 with an immediate byte offset (invisible to hipcc's waitcnt pass)
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-template <int N, class F> RP_DEV void static_for(F&& f) {
-  if constexpr (N > 0) {
-    static_for<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
-
-constexpr int NTOK = 576;
-constexpr int KST = 68;   // LDS row stride (floats) for tiles read along d with ds_read_b128
-constexpr int NTILE = NTOK / 32;
 
 struct AttnP {
   const float* q; const float* k; const float* v;
@@ -47,53 +30,6 @@ struct AttnP {
   float* pst;       // SAVEP only: [ZH][18 query blocks][18 key tiles][32 queries][32 keys]: exp2(s - running max) of every tile, and
   float* mrun;      // [ZH][18 key tiles][576 queries]: the running max (log2 units) each tile was normalised with
 };
-
-// cooperative global -> register prefetch of a [32][64] tile (32 rows x 16 float4).  No exec-masked guards: when the
-// thread count does not divide 512 the surplus threads of the last round re-load (and later re-store) element 511-ish
-// duplicates -- a guarded load becomes its own basic block and hipcc then drains vmcnt(0) before every one of them.
-template <int NT>
-RP_DEV void tile_gload(const float* base, int ld, int tid, float4 (&r)[(512 + NT - 1) / NT]) {
-#pragma unroll
-  for (int j = 0; j < (512 + NT - 1) / NT; ++j) {
-    int f = tid + NT * j;
-    if (512 % NT != 0) f = min(f, 511);
-    r[j] = ld4(base + (long long)(f >> 4) * ld + (f & 15) * 4);
-  }
-}
-template <int NT, int STRIDE>
-RP_DEV void tile_sstore(float* s, int tid, const float4 (&r)[(512 + NT - 1) / NT]) {
-#pragma unroll
-  for (int j = 0; j < (512 + NT - 1) / NT; ++j) {
-    int f = tid + NT * j;
-    if (512 % NT != 0) f = min(f, 511);
-    st4(s + (f >> 4) * STRIDE + (f & 15) * 4, r[j]);
-  }
-}
-
-// S^T tile: s[r] = sum_d Ks[kv = acc_row(r,hi)][d] * breg[q = l31][d]; breg[t] holds d = 32*hi + t (fp32 mode) / bpk[c] = the
-// same 32 values as 4 x 8 bf16 (bf16 mode, see common.h)
-template <bool BF>
-RP_DEV f32x16 score_tile(const float* Ks, int l31, int hi, const float (&breg)[32], const bf16x8 (&bpk)[4]) {
-  f32x16 s = zero16();
-  const float* kr = Ks + l31 * KST + 32 * hi;
-  if (BF) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float4 x = ld4(kr + 8 * c), y = ld4(kr + 8 * c + 4);
-      s = mfma_bf(pack8(x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w), bpk[c], s);
-    }
-    return s;
-  }
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float4 kf = ld4(kr + 4 * c);
-    s = mfma32(kf.x, breg[4 * c + 0], s);
-    s = mfma32(kf.y, breg[4 * c + 1], s);
-    s = mfma32(kf.z, breg[4 * c + 2], s);
-    s = mfma32(kf.w, breg[4 * c + 3], s);
-  }
-  return s;
-}
 
 // acc^T[d][owner] += sum_t Ts[t = acc_row(r,hi)][d] * p[r]   for the two 32-wide d blocks (row-pattern reads)
 template <int STRIDE, bool BF>
@@ -128,31 +64,6 @@ RP_DEV void store_ownerT(float* row_ptr, int hi, const f32x16& o0, const f32x16&
   for (int g = 0; g < 4; ++g) {
     st4(row_ptr + 8 * g + 4 * hi, make_float4(o0[4 * g] * mul, o0[4 * g + 1] * mul, o0[4 * g + 2] * mul, o0[4 * g + 3] * mul));
     st4(row_ptr + 32 + 8 * g + 4 * hi, make_float4(o1[4 * g] * mul, o1[4 * g + 1] * mul, o1[4 * g + 2] * mul, o1[4 * g + 3] * mul));
-  }
-}
-
-// column sums of the same acc^T tile over its 32 owner rows (x mul): part[d] for d = 0..63 -- a partial of the bias gradient of the
-// Linear that produced the operand (qkv), so that gradient needs no pass of its own over the [tokens, 576] tensor.  Register r of a
-// 32-lane half holds column d = acc_row(r, hi) (+32 for o1) of 32 different rows: DPP row sums + one cross-row exchange, fixed order.
-RP_DEV void colsum_ownerT(float* part, int l31, int hi, const f32x16& o0, const f32x16& o1, float mul) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    float a = row16_sum(o0[r]), b = row16_sum(o1[r]);
-    a += __shfl_xor(a, 16, 64);
-    b += __shfl_xor(b, 16, 64);
-    if (l31 == 0) {
-      part[acc_row(r, hi)] = a * mul;
-      part[32 + acc_row(r, hi)] = b * mul;
-    }
-  }
-}
-
-// load the owner operand (32 rows x 64) into registers: lane (row l31, half hi) keeps cols 32*hi .. +31
-RP_DEV void load_owner(const float* row_ptr, int hi, float mul, float (&reg)[32]) {
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float4 x = ld4(row_ptr + 32 * hi + 4 * c);
-    reg[4 * c + 0] = x.x * mul; reg[4 * c + 1] = x.y * mul; reg[4 * c + 2] = x.z * mul; reg[4 * c + 3] = x.w * mul;
   }
 }
 
@@ -777,7 +688,7 @@ __global__ __launch_bounds__(NW * 64, 4) void ds_matmul_kernel(DsMmP p) {
 }
 
 // rp_ds_matmul_t: the same product for tiles stored by store_tile_runs (what attn_bwd_dkdv_p_kernel writes with four contiguous 16-byte
-// stores per lane straight from its accumulators).  Both operands reach LDS by LDS-DMA (global_load_lds_dwordx4: no VGPR, no ds_write,
+// stores per lane straight from its accumulators).  Both operands reach LDS by LDS-DMA (glds16 of common.h: no VGPR, no ds_write,
 // nothing to wait for but vmcnt) -- the wave's own dS tile, 4 KB, gathered into T[j][i] row-major in a wave-private double buffer, and the
 // 32 x 64 rows of b shared by the workgroup -- and feed the matrix pipe through conflict-free ds_read_b32 with
 // immediate offsets: k-step s pairs column j = 2 s + hi with the two half-waves, lane (i = l31, hi) reads T[2 s + hi][i] as the B operand
@@ -873,11 +784,11 @@ __global__ __launch_bounds__(NW * 64, 3) void ds_matmul_t16_kernel(DsMmP p) {
       glds16(uniform_ptr(bb + (long long)(t * 32 + 4 * piece) * p.ldb), bvoff, bs0 + buf * 8192 + piece * 1024);
     }
   };
-  f32x4 acc[4][2];
+  f32x4v acc[4][2];
 #pragma unroll
   for (int m = 0; m < 4; ++m)
 #pragma unroll
-    for (int n = 0; n < 2; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 2; ++n) acc[m][n] = f32x4v{0.f, 0.f, 0.f, 0.f};
   // per-lane read offsets (floats) inside a tile image; k-step ks adds 4 rows
   int aoff[4], boff[2];
 #pragma unroll
@@ -902,7 +813,7 @@ __global__ __launch_bounds__(NW * 64, 3) void ds_matmul_t16_kernel(DsMmP p) {
 #pragma unroll
       for (int m = 0; m < 4; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], bv[n], acc[m][n], 0, 0, 0);
+        for (int n = 0; n < 2; ++n) acc[m][n] = mfma16(av[m], bv[n], acc[m][n]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1027,11 +938,11 @@ __global__ __launch_bounds__(NW * 64, 3) void ds_matmul16_kernel(DsMmP p) {
   // m = 1 adds 16 to i: r + 8, same hh
   const float* arow = p.ds + ((long long)zh * NTILE + (i0 >> 5)) * NTILE * 1024 + ((l15 & 3) + 4 * (l15 >> 3)) * 64 + 32 * ((l15 >> 2) & 1) + 8 * kq;
 
-  f32x4 acc[2][4];
+  f32x4v acc[2][4];
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4v{0.f, 0.f, 0.f, 0.f};
   float4 bpre[NPF];
   float4 a0[4], a1[4], a2[4];      // [2 m][2 halves of 8 floats]
   auto aload = [&](float4 (&a)[4], int t) {
@@ -1069,8 +980,8 @@ __global__ __launch_bounds__(NW * 64, 3) void ds_matmul16_kernel(DsMmP p) {
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
         const float bv = br[16 * n];
-        acc[0][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv, av[0][s_], acc[0][n], 0, 0, 0);
-        acc[1][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv, av[1][s_], acc[1][n], 0, 0, 0);
+        acc[0][n] = mfma16(bv, av[0][s_], acc[0][n]);
+        acc[1][n] = mfma16(bv, av[1][s_], acc[1][n]);
       }
     }
     if (t + 1 < NTILE) bstore(Bs[(t & 1) ^ 1]);

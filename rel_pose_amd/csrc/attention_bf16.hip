@@ -2,14 +2,14 @@
 //
 // Same operation as attention.hip (reference Attention.forward, src/modules/vision_transformer.py:325-329, and its autograd), but q / k / v
 // / o / dO and the gradients live in HBM as bf16 and reach the matrix pipe without a conversion instruction:
-//   * K / V (forward), Q / dO (backward) tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4: 16 bytes per lane, 8 rows of 64 bf16
+//   * K / V (forward), Q / dO (backward) tiles go global -> LDS by LDS-DMA (glds16 of common.h: 16 bytes per lane, 8 rows of 64 bf16
 //     per wave instruction), two stages, one barrier per stage.  The DMA writes LDS lane-linearly, so a row is 8 unpadded 16-byte chunks
 //     whose index is XOR-swizzled on the DMA's SOURCE address and on the reading address.
 //   * an operand that is contracted along its contiguous index (K in S = K Q^T: lane = key, 8 consecutive d) is ONE ds_read_b128 =
 //     one v_mfma_f32_32x32x16_bf16 operand;
-//   * an operand that is contracted along its ROW index (V in O^T = V^T P: lane = d, 8 keys) comes from ds_read_b64_tr_b16, the gfx950
-//     transpose read (within a 16-lane group lane t points at 4 contiguous elements of row t >> 2, columns 4 (t & 3)..; it receives
-//     column t of the four rows -- tools/lab/tr_probe.hip): two reads per operand, no packing;
+//   * an operand that is contracted along its ROW index (V in O^T = V^T P: lane = d, 8 keys) comes from tr_operand (bf16_path.h),
+//     the gfx950 LDS transpose read (within a 16-lane group lane t points at 4 contiguous elements of row t >> 2, columns
+//     4 (t & 3)..; it receives column t of the four rows -- tools/lab/tr_probe.hip): two reads per operand, no packing;
 //   * P is packed once per tile with v_cvt_pk_bf16_f32 straight from the score accumulators (the S^T accumulators ARE the B operand
 //     of the second product: register r of half-wave hi is key acc_row(r, hi), and the k-slot <-> key assignment of that MFMA is chosen
 //     to match: slot j of half hi in step c = key 16 c + 8 (j >> 2) + 4 hi + (j & 3));
@@ -76,15 +76,15 @@ __global__ __launch_bounds__(NW * 64 * GR, (NW * GR + 3) / 4 >= 3 ? 3 : 4) void 
     kvoff[i] = (unsigned)(r * p.ldk + (((lane & 7) ^ swz_k(r)) << 3)) * 2u;
     vvoff[i] = (unsigned)(r * p.ldv + (((lane & 7) ^ swz_v(r)) << 3)) * 2u;
   }
-  const unsigned ks0 = lds_addr_of(&Ks[0][0]) + wave * 2048, vs0 = lds_addr_of(&Vs[0][0]) + wave * 2048;
+  const unsigned ks0 = lds_byte_addr(&Ks[0][0]) + wave * 2048, vs0 = lds_byte_addr(&Vs[0][0]) + wave * 2048;
   auto issue = [&](int s, int buf) {
-    const void* kk = uniform_vptr(kb + (long long)s * SK * p.ldk);
-    glds16b(kk, kvoff[0], ks0 + buf * (ST_EL * 2));
-    glds16b(kk, kvoff[1], ks0 + buf * (ST_EL * 2) + 1024);
+    const void* kk = uniform_ptr(kb + (long long)s * SK * p.ldk);
+    glds16(kk, kvoff[0], ks0 + buf * (ST_EL * 2));
+    glds16(kk, kvoff[1], ks0 + buf * (ST_EL * 2) + 1024);
     if (!STATS) {
-      const void* vv = uniform_vptr(vb + (long long)s * SK * p.ldv);
-      glds16b(vv, vvoff[0], vs0 + buf * (ST_EL * 2));
-      glds16b(vv, vvoff[1], vs0 + buf * (ST_EL * 2) + 1024);
+      const void* vv = uniform_ptr(vb + (long long)s * SK * p.ldv);
+      glds16(vv, vvoff[0], vs0 + buf * (ST_EL * 2));
+      glds16(vv, vvoff[1], vs0 + buf * (ST_EL * 2) + 1024);
     }
   };
 
@@ -184,13 +184,12 @@ int launch_fwd(const AttnBfP& p, hipStream_t st) {
   return RP_OK;
 }
 
-
 // ------------------------------------------------------------------------------------------------
 // backward on the bf16 data path: RECOMPUTE form, two deterministic kernels, no stored dS (at bf16 MFMA rates the two extra score
 // products of the second pass cost less than writing and re-reading 576 x 576 x 2 bytes per head: ~1 GB per layer at 128 pairs).
 //   P = exp2(S cs - lse2);  dP = dO V^T;  dS = P o (dP - delta);  dV = P^T dO;  dK = scale dS^T Q;  dQ = scale dS K
 //   dkdv: a wave owns 32 keys (K, V rows as MFMA B operands in VGPRs) and streams {Q, dO} stages; S, dP: A = Q / dO rows (ds_read_b128);
-//         dV^T += dO^T P, dK^T += Q^T dS: A = the SAME LDS tiles read by ds_read_b64_tr_b16, B = P / dS packed from the accumulators.
+//         dV^T += dO^T P, dK^T += Q^T dS: A = the SAME LDS tiles read by tr_operand, B = P / dS packed from the accumulators.
 //   dq  : a wave owns 32 queries (Q, dO rows in VGPRs, lse2 / delta lane-local) and streams {K, V} stages; S^T, dP^T: A = K / V rows;
 //         dQ^T += K^T dS^T: A = the K tile by transpose reads.
 // Tiles that are read both ways use the swizzle swz_d: (row >> 1) & 7 bit-reversed, so that the four rows of a transpose-read block
@@ -232,14 +231,14 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 3 : 2) void attn_bwd_dkdv_bf16_k
     qvoff[i] = (unsigned)(r * p.ldq + (((lane & 7) ^ swz_d(r)) << 3)) * 2u;
     dvoff[i] = (unsigned)(r * p.lddo + (((lane & 7) ^ swz_d(r)) << 3)) * 2u;
   }
-  const unsigned qs0 = lds_addr_of(&Qs[0][0]) + wave * 2048, ds0 = lds_addr_of(&Ds[0][0]) + wave * 2048;
+  const unsigned qs0 = lds_byte_addr(&Qs[0][0]) + wave * 2048, ds0 = lds_byte_addr(&Ds[0][0]) + wave * 2048;
   auto issue = [&](int s, int buf) {
-    const void* qq = uniform_vptr(qb + (long long)s * SQ * p.ldq);
-    const void* dd = uniform_vptr(dob + (long long)s * SQ * p.lddo);
-    glds16b(qq, qvoff[0], qs0 + buf * (ST_EL * 2));
-    glds16b(qq, qvoff[1], qs0 + buf * (ST_EL * 2) + 1024);
-    glds16b(dd, dvoff[0], ds0 + buf * (ST_EL * 2));
-    glds16b(dd, dvoff[1], ds0 + buf * (ST_EL * 2) + 1024);
+    const void* qq = uniform_ptr(qb + (long long)s * SQ * p.ldq);
+    const void* dd = uniform_ptr(dob + (long long)s * SQ * p.lddo);
+    glds16(qq, qvoff[0], qs0 + buf * (ST_EL * 2));
+    glds16(qq, qvoff[1], qs0 + buf * (ST_EL * 2) + 1024);
+    glds16(dd, dvoff[0], ds0 + buf * (ST_EL * 2));
+    glds16(dd, dvoff[1], ds0 + buf * (ST_EL * 2) + 1024);
   };
   issue(0, 0);
 
@@ -311,8 +310,8 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 3 : 2) void attn_bwd_dkdv_bf16_k
   }
   if (p.dk_colpart) {
     const long long prow = ((long long)z * 18 + (k0 >> 5)) * p.ldp + h * 64;
-    colsum_ownerT_bf(p.dv_colpart + prow, l31, hi, dv0, dv1, 1.0f);
-    colsum_ownerT_bf(p.dk_colpart + prow, l31, hi, dk0, dk1, p.scale);
+    colsum_ownerT(p.dv_colpart + prow, l31, hi, dv0, dv1, 1.0f);
+    colsum_ownerT(p.dk_colpart + prow, l31, hi, dk0, dk1, p.scale);
   }
   __builtin_amdgcn_s_barrier();                  // every wave is done with the stage buffers
   bf16_t* Os = &Qs[0][0] + wave * 2048;
@@ -342,14 +341,14 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_bwd_dq_bf16_kernel(AttnBwdBfP
     kvoff[i] = (unsigned)(r * p.ldk + (((lane & 7) ^ swz_d(r)) << 3)) * 2u;      // K is read both ways
     vvoff[i] = (unsigned)(r * p.ldv + (((lane & 7) ^ swz_k(r)) << 3)) * 2u;      // V by rows only
   }
-  const unsigned ks0 = lds_addr_of(&Ks[0][0]) + wave * 2048, vs0 = lds_addr_of(&Vs[0][0]) + wave * 2048;
+  const unsigned ks0 = lds_byte_addr(&Ks[0][0]) + wave * 2048, vs0 = lds_byte_addr(&Vs[0][0]) + wave * 2048;
   auto issue = [&](int s, int buf) {
-    const void* kk = uniform_vptr(kb + (long long)s * SK * p.ldk);
-    const void* vv = uniform_vptr(vb + (long long)s * SK * p.ldv);
-    glds16b(kk, kvoff[0], ks0 + buf * (ST_EL * 2));
-    glds16b(kk, kvoff[1], ks0 + buf * (ST_EL * 2) + 1024);
-    glds16b(vv, vvoff[0], vs0 + buf * (ST_EL * 2));
-    glds16b(vv, vvoff[1], vs0 + buf * (ST_EL * 2) + 1024);
+    const void* kk = uniform_ptr(kb + (long long)s * SK * p.ldk);
+    const void* vv = uniform_ptr(vb + (long long)s * SK * p.ldv);
+    glds16(kk, kvoff[0], ks0 + buf * (ST_EL * 2));
+    glds16(kk, kvoff[1], ks0 + buf * (ST_EL * 2) + 1024);
+    glds16(vv, vvoff[0], vs0 + buf * (ST_EL * 2));
+    glds16(vv, vvoff[1], vs0 + buf * (ST_EL * 2) + 1024);
   };
   issue(0, 0);
 
@@ -400,7 +399,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_bwd_dq_bf16_kernel(AttnBwdBfP
       dq1 = mfma_bf(tr_operand(Kt + 1024 + toff[1][0], Kt + 1024 + toff[1][1]), s1, dq1);
     }
   }
-  if (p.dq_colpart) colsum_ownerT_bf(p.dq_colpart + ((long long)z * 18 + (q0 >> 5)) * p.ldp + h * 64, l31, hi, dq0, dq1, p.scale);
+  if (p.dq_colpart) colsum_ownerT(p.dq_colpart + ((long long)z * 18 + (q0 >> 5)) * p.ldp + h * 64, l31, hi, dq0, dq1, p.scale);
   __builtin_amdgcn_s_barrier();
   store_ownerT_bf16(&Ks[0][0] + wave * 2048, p.dq + ((long long)z * NTOK + q0) * p.lddq + h * 64, p.lddq, lane, dq0, dq1, p.scale);
 }

@@ -24,17 +24,16 @@ constexpr int BN_MAXC = 256;
 // convolution -- 6.3 ms of the 34 ms step at 128 pairs, profiles/r2_bf16_128pairs_full_step_summary.txt).  All arithmetic, the
 // statistics and the per-channel parameters stay fp32 / double; bf16 values are widened exactly on load and rounded to nearest-even
 // on store.
-typedef unsigned short bf16s;      // storage only
 template <typename T> RP_DEV float4 ldv(const T* p);
 template <> RP_DEV float4 ldv<float>(const float* p) { return ld4(p); }
-template <> RP_DEV float4 ldv<bf16s>(const bf16s* p) {
+template <> RP_DEV float4 ldv<bf16_t>(const bf16_t* p) {
   const uint2 w = *reinterpret_cast<const uint2*>(p);
   return make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
                      __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
 }
 template <typename T> RP_DEV void stv(T* p, float4 v);
 template <> RP_DEV void stv<float>(float* p, float4 v) { st4(p, v); }
-template <> RP_DEV void stv<bf16s>(bf16s* p, float4 v) { *reinterpret_cast<uint2*>(p) = make_uint2(pk_bf16(v.x, v.y), pk_bf16(v.z, v.w)); }
+template <> RP_DEV void stv<bf16_t>(bf16_t* p, float4 v) { *reinterpret_cast<uint2*>(p) = make_uint2(pk_bf16(v.x, v.y), pk_bf16(v.z, v.w)); }
 // G float4 groups (4 G channels) per thread and access: 1 for fp32 (16 bytes); 2 for bf16 storage when C % 8 == 0 -- with 8-byte accesses the bf16
 // passes were INSTRUCTION-bound (the same bytes took 1.5x the fp32 kernels' time: profiles/r6_ab.txt), with 16-byte accesses they are HBM-bound
 template <typename T, int G> RP_DEV void ldg(const T* p, float4 (&v)[G]) {
@@ -62,7 +61,7 @@ static bool bn_wide(int bf16, int C) {
 }
 template <typename T> RP_DEV float ld1(const T* p);
 template <> RP_DEV float ld1<float>(const float* p) { return *p; }
-template <> RP_DEV float ld1<bf16s>(const bf16s* p) { return __builtin_bit_cast(float, (unsigned)(*p) << 16); }
+template <> RP_DEV float ld1<bf16_t>(const bf16_t* p) { return __builtin_bit_cast(float, (unsigned)(*p) << 16); }
 
 // the normalisation, written with explicit fmas: the backward kernels re-evaluate it to rebuild the ReLU mask from x alone
 // (no residual), and must get bit-identical values
@@ -506,7 +505,7 @@ static int bn_stats_t(const T* x, long long R, int C, double* partial, float* me
 extern "C" int rp_bn_stats(const void* x, long long R, int C, double* partial, float* mean, float* rstd, float* running_mean,
                            float* running_var, float momentum, float eps, int bf16, void* stream) {
   if (int e = bn_check(R, C)) return e;
-  if (bf16) return bn_stats_t((const bf16s*)x, R, C, partial, mean, rstd, running_mean, running_var, momentum, eps, (hipStream_t)stream);
+  if (bf16) return bn_stats_t((const bf16_t*)x, R, C, partial, mean, rstd, running_mean, running_var, momentum, eps, (hipStream_t)stream);
   return bn_stats_t((const float*)x, R, C, partial, mean, rstd, running_mean, running_var, momentum, eps, (hipStream_t)stream);
 }
 
@@ -527,10 +526,10 @@ extern "C" int rp_bn_apply_fwd(const void* x, const float* mean, const float* rs
                                const void* residual, void* y, long long R, int C, int relu, int bf16, void* stream) {
   if (int e = bn_check(R, C)) return e;
   const long long n4 = R * C / 4;
-  if (bn_wide(bf16, C)) hipLaunchKernelGGL((bn_apply_fwd_kernel<bf16s, 2>), dim3(apply_grid(n4 / 2)), dim3(256), 0, (hipStream_t)stream, (const bf16s*)x,
-                                           mean, rstd, gamma, beta, (const bf16s*)residual, (bf16s*)y, n4 / 2, C / 8, relu);
-  else if (bf16) hipLaunchKernelGGL((bn_apply_fwd_kernel<bf16s, 1>), dim3(apply_grid(n4)), dim3(256), 0, (hipStream_t)stream, (const bf16s*)x, mean,
-                                    rstd, gamma, beta, (const bf16s*)residual, (bf16s*)y, n4, C / 4, relu);
+  if (bn_wide(bf16, C)) hipLaunchKernelGGL((bn_apply_fwd_kernel<bf16_t, 2>), dim3(apply_grid(n4 / 2)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                                           mean, rstd, gamma, beta, (const bf16_t*)residual, (bf16_t*)y, n4 / 2, C / 8, relu);
+  else if (bf16) hipLaunchKernelGGL((bn_apply_fwd_kernel<bf16_t, 1>), dim3(apply_grid(n4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, mean,
+                                    rstd, gamma, beta, (const bf16_t*)residual, (bf16_t*)y, n4, C / 4, relu);
   else hipLaunchKernelGGL((bn_apply_fwd_kernel<float, 1>), dim3(apply_grid(n4)), dim3(256), 0, (hipStream_t)stream, (const float*)x, mean, rstd, gamma,
                           beta, (const float*)residual, (float*)y, n4, C / 4, relu);
   RP_CHECK_LAUNCH();
@@ -574,7 +573,7 @@ extern "C" int rp_bn_bwd(const void* dy, const void* y, const void* x, const flo
                          double* partial, float* c12, long long R, int C, int relu, int training, int bf16, void* stream) {
   if (int e = bn_check(R, C)) return e;
   if (relu && !y && !beta) return RP_EBADSHAPE;
-  if (bf16) return bn_bwd_t((const bf16s*)dy, (const bf16s*)y, (const bf16s*)x, mean, rstd, gamma, beta, (bf16s*)dx, (bf16s*)dres, dgamma, dbeta,
+  if (bf16) return bn_bwd_t((const bf16_t*)dy, (const bf16_t*)y, (const bf16_t*)x, mean, rstd, gamma, beta, (bf16_t*)dx, (bf16_t*)dres, dgamma, dbeta,
                             partial, c12, R, C, relu, training, (hipStream_t)stream);
   return bn_bwd_t((const float*)dy, (const float*)y, (const float*)x, mean, rstd, gamma, beta, (float*)dx, (float*)dres, dgamma, dbeta, partial,
                   c12, R, C, relu, training, (hipStream_t)stream);
@@ -682,7 +681,7 @@ extern "C" int rp_maxpool3x3s2_fwd(const void* x, void* y, unsigned char* idx, i
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return RP_EBADSHAPE;
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   const long long total = (long long)N * OH * OW * (C / 4);
-  if (bf16) hipLaunchKernelGGL(maxpool_fwd_kernel<bf16s>, dim3(apply_grid(total)), dim3(256), 0, (hipStream_t)stream, (const bf16s*)x, (bf16s*)y, idx,
+  if (bf16) hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(apply_grid(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, idx,
                                N, H, W, C, OH, OW);
   else hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(apply_grid(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, idx, N, H,
                           W, C, OH, OW);
@@ -694,14 +693,13 @@ extern "C" int rp_maxpool3x3s2_bwd(const void* dy, const unsigned char* idx, voi
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return RP_EBADSHAPE;
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   const long long total = (long long)N * H * W * (C / 4);
-  if (bf16) hipLaunchKernelGGL(maxpool_bwd_kernel<bf16s>, dim3(apply_grid(total)), dim3(256), 0, (hipStream_t)stream, (const bf16s*)dy, idx, (bf16s*)dx,
+  if (bf16) hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(apply_grid(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, idx, (bf16_t*)dx,
                                N, H, W, C, OH, OW);
   else hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(apply_grid(total)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, idx, (float*)dx, N,
                           H, W, C, OH, OW);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
-
 
 // ---- stem: BatchNorm + ReLU + 3x3/2 max-pool as one pass (forward) and without the pool-backward tensor (backward) -------------
 namespace {
@@ -833,10 +831,10 @@ extern "C" int rp_bn_relu_pool_fwd(const void* x, const float* mean, const float
   if (int e = bn_check((long long)N * H * W, C)) return e;
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   const long long total = (long long)N * OH * OW * (C / 4);
-  if (bn_wide(bf16, C)) hipLaunchKernelGGL((bn_pool_fwd_kernel<bf16s, 2>), dim3(apply_grid(total / 2)), dim3(256), 0, (hipStream_t)stream, (const bf16s*)x,
-                                           mean, rstd, gamma, beta, (bf16s*)y, idx, N, H, W, C, OH, OW);
-  else if (bf16) hipLaunchKernelGGL((bn_pool_fwd_kernel<bf16s, 1>), dim3(apply_grid(total)), dim3(256), 0, (hipStream_t)stream, (const bf16s*)x, mean, rstd,
-                                    gamma, beta, (bf16s*)y, idx, N, H, W, C, OH, OW);
+  if (bn_wide(bf16, C)) hipLaunchKernelGGL((bn_pool_fwd_kernel<bf16_t, 2>), dim3(apply_grid(total / 2)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                                           mean, rstd, gamma, beta, (bf16_t*)y, idx, N, H, W, C, OH, OW);
+  else if (bf16) hipLaunchKernelGGL((bn_pool_fwd_kernel<bf16_t, 1>), dim3(apply_grid(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, mean, rstd,
+                                    gamma, beta, (bf16_t*)y, idx, N, H, W, C, OH, OW);
   else hipLaunchKernelGGL((bn_pool_fwd_kernel<float, 1>), dim3(apply_grid(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, mean, rstd, gamma,
                           beta, (float*)y, idx, N, H, W, C, OH, OW);
   RP_CHECK_LAUNCH();
@@ -985,7 +983,7 @@ extern "C" int rp_bn_relu_pool_bwd(const void* dp, const unsigned char* idx, con
   const long long R = (long long)N * H * W;
   if (int e = bn_check(R, C)) return e;
   if (R * C >= (1LL << 32)) return RP_EBADSHAPE;                     // 32-bit element indices in the gather
-  if (bf16) return bn_relu_pool_bwd_t((const bf16s*)dp, idx, (const bf16s*)x, mean, rstd, gamma, beta, (bf16s*)dx, dgamma, dbeta, partial, c12, N, H,
+  if (bf16) return bn_relu_pool_bwd_t((const bf16_t*)dp, idx, (const bf16_t*)x, mean, rstd, gamma, beta, (bf16_t*)dx, dgamma, dbeta, partial, c12, N, H,
                                       W, C, training, (hipStream_t)stream);
   return bn_relu_pool_bwd_t((const float*)dp, idx, (const float*)x, mean, rstd, gamma, beta, (float*)dx, dgamma, dbeta, partial, c12, N, H, W, C,
                             training, (hipStream_t)stream);

@@ -1,26 +1,12 @@
-// bf16_path.h -- device helpers shared by the kernels of the bf16 data path (attention_bf16.hip, emm_bf16.hip): LDS-DMA of bf16
-// tiles, transpose-read MFMA operands, the LDS swizzles that serve both read patterns, bf16 row stores of transposed accumulators.
+// bf16_path.h -- device helpers shared by the kernels that feed bf16 MFMAs from LDS: transpose-read MFMA operands (builtin form and the
+// hand-placed asm form with its counted wait), the LDS swizzles that serve both read patterns (attention_bf16.hip, emm_bf16.hip,
+// dx_lnbwd_bf16.hip, dw192_bf16.hip, conv3x3_wgrad_bf16.hip, conv_stem_wgrad_bf16.hip); in namespace bf16path what only the 576-token
+// kernels use: bf16 row stores of transposed accumulators, the swz_d read offsets.  (LDS-DMA of bf16 tiles: glds16 of common.h.)
 #pragma once
 #include "common.h"
 
-namespace bf16path {
-
-constexpr int NTOK = 576;
-typedef unsigned short bf16_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-RP_DEV void glds16b(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(lds_byte_addr), "s"(sbase) : "memory");
-}
-RP_DEV const void* uniform_vptr(const void* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
-RP_DEV unsigned lds_addr_of(const void* p) { return (unsigned)(size_t)(rp_lds_ptr_t)(p); }
 
 // two transpose reads = one bf16x8 MFMA operand: slots 0-3 from the 4-row block at a0, slots 4-7 from the one at a1
 RP_DEV bf16x8 tr_operand(const bf16_t* a0, const bf16_t* a1) {
@@ -31,13 +17,24 @@ RP_DEV bf16x8 tr_operand(const bf16_t* a0, const bf16_t* a1) {
   v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3]; v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
   return __builtin_bit_cast(bf16x8, v);
 }
-RP_DEV bf16x8 ld_bf16x8_lds(const bf16_t* p) { return *reinterpret_cast<const bf16x8*>(p); }
 
-RP_DEV bf16x8 ones8() {
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  u32x4_t w;
-  w[0] = w[1] = w[2] = w[3] = 0x3f803f80u;
-  return __builtin_bit_cast(bf16x8, w);
+// The same transpose read by hand, with an immediate byte offset: hipcc sinks every C++-level LDS read next to its MFMA behind
+// `s_waitcnt lgkmcnt(0)` (conv3x3_bf16.hip explains); a volatile asm read keeps its place.  The matching wait is an asm that passes the
+// four registers of one MFMA's operands through ("+v"), so the MFMA stays behind it; N = reads issued after them that may still be in
+// flight (the LDS queue retires in order).  The compiler does not see these reads: its own waits are only ever stricter than needed.
+template <int IMM>
+RP_DEV void tr_read(unsigned long long& d, unsigned addr) {
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(IMM));
+}
+template <int N>
+RP_DEV void tr_wait(unsigned long long& a, unsigned long long& b, unsigned long long& c, unsigned long long& d) {
+  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
+}
+RP_DEV bf16x8 op8(unsigned long long lo, unsigned long long hi) {      // two tr_read results = one bf16x8 operand
+  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+  u64x2 v;
+  v[0] = lo; v[1] = hi;
+  return __builtin_bit_cast(bf16x8, v);
 }
 
 // LDS image of a K-type stage: row r = 8 chunks of 16 B, chunk c stored at slot c ^ ((r >> 1) & 7)  (ds_read_b128 by lane = row)
@@ -47,6 +44,19 @@ RP_DEV int swz_k(int r) { return (r >> 1) & 7; }
 RP_DEV int swz_v(int r) { return ((r >> 1) & 1) << 2; }
 
 RP_DEV int swz_d(int r) { return (((r >> 1) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 3) & 1); }
+
+namespace bf16path {
+
+constexpr int NTOK = 576;
+
+RP_DEV bf16x8 ld_bf16x8_lds(const bf16_t* p) { return *reinterpret_cast<const bf16x8*>(p); }
+
+RP_DEV bf16x8 ones8() {
+  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+  u32x4_t w;
+  w[0] = w[1] = w[2] = w[3] = 0x3f803f80u;
+  return __builtin_bit_cast(bf16x8, w);
+}
 
 // per-lane element offsets of the transpose reads of one 32-row tile in a swz_d image: [db][half] for the 8-row groups (rows
 // 16 c2 + 8 half + 4 hi + (t16 >> 2), columns 16 g + 4 (t16 & 3) + 32 db); add 1024 c2 for the second 16 rows
@@ -80,20 +90,5 @@ RP_DEV void store_ownerT_bf16(bf16_t* Os, bf16_t* dst, int ld, int lane, const f
     *reinterpret_cast<uint4*>(dst + (long long)row * ld + 8 * ch) = w;
   }
 }
-
-// column sums of the same tile over its 32 owner rows (x mul): part[0..63], fixed order (see attention.hip: colsum_ownerT)
-RP_DEV void colsum_ownerT_bf(float* part, int l31, int hi, const f32x16& o0, const f32x16& o1, float mul) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    float a = row16_sum(o0[r]), b = row16_sum(o1[r]);
-    a += __shfl_xor(a, 16, 64);
-    b += __shfl_xor(b, 16, 64);
-    if (l31 == 0) {
-      part[acc_row(r, hi)] = a * mul;
-      part[32 + acc_row(r, hi)] = b * mul;
-    }
-  }
-}
-
 
 }  // namespace bf16path

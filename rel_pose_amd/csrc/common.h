@@ -1,4 +1,10 @@
-// common.h -- device helpers shared by the gfx950 kernels of librelpose_hip.so.
+// common.h -- device helpers shared by the gfx950 kernels of librelpose_hip.so (and librelpose_readout.so), one definition each:
+//   * MFMA wrappers and accumulator types: mfma32 / mfma_bf (32x32 tiles, f32x16), mfma16 / mfma16bf (16x16 tiles, f32x4v), pack8, acc_row
+//   * GELU forms, log2-domain exp, wave / DPP-row reductions (wave_sum, row16_sum, row16_max, colsum_ownerT), quad_transpose4
+//   * accumulator-image and bf16-row stores (store_acc_image*, st_bf16x8 / ld_bf16x8, widen4), bf16_t
+//   * XCD-aware work order (xcd_problem, xcd_grid) and, host side, resident_slots
+//   * LDS-DMA (glds16, lds_byte_addr, uniform_ptr), the hand-placed LDS read lds_rd32, the compile-time loop static_for
+//   * ld4 / st4 / st4_nt, RP_CHECK_LAUNCH
 //
 // MFMA primitive used everywhere: v_mfma_f32_32x32x2_f32 (exact fp32, 64 FLOP/clk/SIMD, 157 TF chip peak).
 //   A operand: lane l holds A[i = l&31][k = l>>5]      (one fp32 VGPR)
@@ -9,13 +15,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef unsigned short bf16_t;      // bf16 storage only
 
 #define RP_DEV __device__ __forceinline__
 
 RP_DEV f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+// v_mfma_f32_16x16x4_f32 (exact fp32): A lane (i = l&15, k = l>>4), B lane (k = l>>4, j = l&15); reg r of lane l is D[row = 4*(l>>4) + r][col = l&15]
+RP_DEV f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // bf16 operand mode (BASELINE.json configs[4]: "bf16 with MFMA bf16 attention GEMMs"): v_mfma_f32_32x32x16_bf16, fp32
 // accumulate, SAME 32x32 accumulator layout as above.  A operand: lane l holds A[i = l&31][k-slots 8*(l>>5) .. +7] as 8 bf16,
@@ -38,6 +48,8 @@ RP_DEV bf16x8 pack8(float a0, float a1, float a2, float a3, float a4, float a5, 
 }
 RP_DEV bf16x8 pack8(const float* v) { return pack8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]); }
 RP_DEV f32x16 mfma_bf(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+// v_mfma_f32_16x16x32_bf16: same accumulator layout as mfma16; lane (i = l&15, q = l>>4) supplies k-slots 8 q .. 8 q + 7 of a 32-wide k block
+RP_DEV f32x4v mfma16bf(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 // row of accumulator register r for half-wave hi
 RP_DEV constexpr int acc_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
@@ -140,6 +152,23 @@ RP_DEV float row16_max(float v) {
   v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)));
   v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true)));
   return v;
+}
+
+// column sums (x mul) of a wave's transposed 32 x 64 accumulator tile acc^T (lane = owner row l31, register r of o0 / o1 = column
+// acc_row(r, hi) / 32 + acc_row(r, hi)) over its 32 owner rows: part[d] for d = 0..63 -- a partial of the bias gradient of the Linear
+// that produced the operand (qkv), so that gradient needs no pass of its own over the [tokens, 576] tensor.  Register r of a 32-lane
+// half holds one column of 32 different rows: DPP row sums + one cross-row exchange, fixed order.
+RP_DEV void colsum_ownerT(float* part, int l31, int hi, const f32x16& o0, const f32x16& o1, float mul) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float a = row16_sum(o0[r]), b = row16_sum(o1[r]);
+    a += __shfl_xor(a, 16, 64);
+    b += __shfl_xor(b, 16, 64);
+    if (l31 == 0) {
+      part[acc_row(r, hi)] = a * mul;
+      part[32 + acc_row(r, hi)] = b * mul;
+    }
+  }
 }
 
 // 4 x 4 transpose across the four lanes of a DPP quad: before, lane q (= lane & 3) holds a[0..3]; after, it holds b[e] = (a of lane e)[q].
@@ -246,16 +275,33 @@ inline int xcd_grid(int nq, int ZH) { return nq * ((ZH + 7) / 8) * 8; }
 // Inline asm: hipcc drains vmcnt(0) before the next ds_read when it sees the builtin form in flight (the LDS write sits on
 // the VM counter); completion is counted by hand -- s_waitcnt vmcnt(N) by every wave, then s_barrier, then the reads.
 typedef __attribute__((address_space(3))) void* rp_lds_ptr_t;
-RP_DEV void glds16(const float* sbase, unsigned voff, unsigned lds_byte_addr) {
+RP_DEV void glds16(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(voff), "s"(lds_byte_addr), "s"(sbase) : "memory");
 }
-RP_DEV unsigned lds_byte_addr(const float* p) { return (unsigned)(size_t)(rp_lds_ptr_t)(p); }
-RP_DEV const float* uniform_ptr(const float* p) {      // SGPR pair for the DMA base where hipcc cannot prove uniformity
+RP_DEV unsigned lds_byte_addr(const void* p) { return (unsigned)(size_t)(rp_lds_ptr_t)(p); }
+template <class T>
+RP_DEV const T* uniform_ptr(const T* p) {      // SGPR pair for the DMA base where hipcc cannot prove uniformity
   const unsigned long long v = (unsigned long long)p;
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const float*)(((unsigned long long)hi << 32) | lo);
+  return (const T*)(((unsigned long long)hi << 32) | lo);
+}
+
+// ds_read_b32 with an immediate byte offset, by hand: a volatile asm read keeps its place in the instruction stream and is invisible to
+// hipcc's waitcnt pass, so the kernel counts lgkmcnt itself (see the per-kernel comments)
+template <int OFF> RP_DEV float lds_rd32(unsigned addr) {
+  float v;
+  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+  return v;
+}
+
+// compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), for bodies whose asm immediates depend on the index
+template <int N, class F> RP_DEV void static_for(F&& f) {
+  if constexpr (N > 0) {
+    static_for<N - 1>(f);
+    f(std::integral_constant<int, N - 1>{});
+  }
 }
 
 RP_DEV float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -263,6 +309,17 @@ RP_DEV void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 RP_DEV void st4_nt(float* p, float4 v) {      // non-temporal: for data a LATER kernel reads (it would only displace what this one re-reads)
   typedef float f4v __attribute__((ext_vector_type(4)));
   __builtin_nontemporal_store(f4v{v.x, v.y, v.z, v.w}, reinterpret_cast<f4v*>(p));
+}
+
+// host: workgroups of KERNEL (NT threads, no dynamic LDS) the device holds at once = CUs x resident workgroups per CU: the grid of a
+// persistent kernel.  Two runtime queries: every caller keeps the result in a function-local static of its own.
+template <auto KERNEL, int NT>
+inline int resident_slots() {
+  int dev = 0, cus = 256, per_cu = 1;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, NT, 0);
+  return cus * (per_cu > 0 ? per_cu : 1);
 }
 
 #define RP_CHECK_LAUNCH()                         \

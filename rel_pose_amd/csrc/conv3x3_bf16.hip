@@ -24,13 +24,11 @@
 //     M-tile (position x 16 + hi x plane) plus an immediate (k-step plane pair, tap offset): no address arithmetic in the main loop;
 //   * halo store (ds_write_b128; 8 consecutive lanes = the 8 chunks of one position): 349 mod 16 = 13 is odd, so the 8 planes of a
 //     position land in 8 different 16-byte bank groups.
-#include <type_traits>
 #include "common.h"
 #include "../../include/relpose_hip.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 constexpr int C = 64;                    // channels in and out
 constexpr int IW = 56, IH = 56;          // image size
 constexpr int TH = 4;                    // output rows per tile
@@ -59,13 +57,6 @@ struct ConvP {
   int ntiles;            // N * 14
 };
 
-template <int I, int N, class F>
-RP_DEV void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 // operand read by hand: hipcc sinks every C++-level LDS read next to its MFMA (one register set, `s_waitcnt lgkmcnt(0)` in between:
 // a full LDS round trip per MFMA group with one wave per SIMD), whatever the source order or the sched_group_barrier hints say.
 // A volatile asm read keeps its place; the matching wait is an asm that passes the registers through ("+v"), so the MFMAs stay behind
@@ -221,10 +212,10 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_c64_kernel(ConvP p) {
 #pragma unroll
       for (int j = 0; j < MT; ++j) lds_read128<2 * ks * PLANE + (r * HC + s_) * 16>(d[j], ea[j]);
     };
-    static_for<0, DEPTH>([&](auto d) { lda(d, a[decltype(d)::value]); });
+    static_for<DEPTH>([&](auto d) { lda(d, a[decltype(d)::value]); });
     const int tn1 = min(t + 1, t1 - 1), tn2 = min(t + 2, t1 - 1);
     const bool more2 = t + 2 < t1;
-    static_for<0, 36>([&](auto stepc) {
+    static_for<36>([&](auto stepc) {
       constexpr int step = decltype(stepc)::value;
       if constexpr (step + DEPTH < 36) lda(std::integral_constant<int, step + DEPTH>{}, a[(step + DEPTH) % (DEPTH + 1)]);
       constexpr int ahead = (step + DEPTH < 36 ? DEPTH : 35 - step) * MT;      // reads issued after this group's

@@ -18,7 +18,6 @@
 //   * a tile needs input rows y - 1 .. y + 4 and fetches only the four new ones through registers while the previous tile computes; they
 //     replace rows the previous tile was still reading, so they are written between two barriers (57 KB per 2016 MFMAs per wave: ~1 %);
 //     rows outside the image read a seventh, permanently zero slot (an address select per tile, no branch in the loop).
-#include <type_traits>
 #include "common.h"
 #include "../../include/relpose_hip.h"
 
@@ -46,18 +45,6 @@ struct CvG {
   int CO;               // 128 or 192 (multiple of 64)
   int dgrad;            // 1: the filter W'[ci][r][s][co] = W[co][2 - r][2 - s][ci] is read out of the forward weight (CO == 128 only)
 };
-
-template <int OFF> RP_DEV float rd32g(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-template <int N, class F> RP_DEV void sforg(F&& f) {
-  if constexpr (N > 0) {
-    sforg<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
 
 __global__ __launch_bounds__(256, 1) void conv3x3_c128_f32_kernel(CvG p) {
   __shared__ __attribute__((aligned(16))) float Xr[NSLOT + 1][ROWF];      // 109 984 B
@@ -179,29 +166,29 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c128_f32_kernel(CvG p) {
         slot = (yin < 0 || yin >= IH) ? NSLOT : slot;
         xa[j][r] = xs0 + (unsigned)(slot * ROWF + ocol[j] * PS + kq) * 4u;
       }
-    f32x4 acc[NBLK];
+    f32x4v acc[NBLK];
 #pragma unroll
-    for (int j = 0; j < NBLK; ++j) acc[j] = f32x4{bv.x, bv.y, bv.z, bv.w};
+    for (int j = 0; j < NBLK; ++j) acc[j] = f32x4v{bv.x, bv.y, bv.z, bv.w};
     // Two operand register sets, picked by the k-step's parity at compile time; the seven reads of k-step k + 1 go out ONE BEHIND EACH MFMA
     // of k-step k, and each MFMA waits only for ITS operand: the LDS queue retires in order and exactly six younger reads are in flight in
     // front of it -- lgkmcnt(6) (conv3x3_f32.hip).
     float b0[NBLK], b1[NBLK];
 #pragma unroll
-    for (int j = 0; j < NBLK; ++j) b0[j] = rd32g<0>(xa[j][0]);
-    sforg<9 * KS>([&](auto kc) {
+    for (int j = 0; j < NBLK; ++j) b0[j] = lds_rd32<0>(xa[j][0]);
+    static_for<9 * KS>([&](auto kc) {
       constexpr int k = kc, tap = k / KS, kk = k % KS;
       float (&bc)[NBLK] = (k & 1) ? b1 : b0;
       float (&bn)[NBLK] = (k & 1) ? b0 : b1;
-      sforg<NBLK>([&](auto jc) {
+      static_for<NBLK>([&](auto jc) {
         constexpr int j = jc;
         if constexpr (k + 1 < 9 * KS) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(bc[j]));
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bc[j]));
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[tap][kk], bc[j], acc[j], 0, 0, 0);
+        acc[j] = mfma16(wreg[tap][kk], bc[j], acc[j]);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (k + 1 < 9 * KS) {
           constexpr int k1 = k + 1, tap1 = k1 / KS, kk1 = k1 % KS, r1 = tap1 / 3, s1 = tap1 % 3;
           constexpr int off = (s1 * PS + 4 * kk1) * 4;
-          bn[j] = rd32g<off>(xa[j][r1]);
+          bn[j] = lds_rd32<off>(xa[j][r1]);
           __builtin_amdgcn_sched_barrier(0);
         }
       });

@@ -20,7 +20,6 @@
 //   * operands are read one k-step ahead by asm ds_read_b32, one read behind each MFMA, with a counted wait per MFMA written out by hand
 //     (hipcc sinks C++-level reads next to their MFMAs behind lgkmcnt(0)); the accumulators (co = rows, pixels = columns) leave as one
 //     16-byte store per lane and block.
-#include <type_traits>
 #include "common.h"
 #include "../../include/relpose_hip.h"
 
@@ -49,18 +48,6 @@ struct CvF {
   int dgrad;            // 0: filter W[co][r][s][ci] as it lies; 1: the input gradient's filter W'[ci][r][s][co] = W[co][2 - r][2 - s][ci], read
                         // from the SAME forward weight (strided, 144 loads per lane once per workgroup: no rotated copy, no extra launch)
 };
-
-template <int OFF> RP_DEV float rd32c(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-template <int N, class F> RP_DEV void sforc(F&& f) {
-  if constexpr (N > 0) {
-    sforc<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
 
 // RES / BN: the epilogue options as TEMPLATE parameters -- as run-time branches of one kernel they cost the plain launches 15 us each (294 -> 406
 // registers and a different schedule around the tile loop: profiles/r6_ab.txt), more than the passes they replace bring
@@ -178,9 +165,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_f32_kernel(CvF p) {
         slot = (yin < 0 || yin >= IH) ? NSLOT : slot;
         xa[j][r] = xs0 + (unsigned)(slot * ROWF + ocol[j] * PS + kq) * 4u;
       }
-    f32x4 acc[NBLK];
+    f32x4v acc[NBLK];
 #pragma unroll
-    for (int j = 0; j < NBLK; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NBLK; ++j) acc[j] = f32x4v{0.f, 0.f, 0.f, 0.f};
     float4 rv[NBLK], bx[NBLK];                               // the residual / the BatchNorm input at this tile's outputs, requested a tile's worth of MFMAs early
     if constexpr (RES) {
 #pragma unroll
@@ -195,21 +182,21 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_f32_kernel(CvF p) {
     // waits only for ITS operand: the LDS queue retires in order and exactly six younger reads are in flight in front of it -- lgkmcnt(6).
     float b0[NBLK], b1[NBLK];
 #pragma unroll
-    for (int j = 0; j < NBLK; ++j) b0[j] = rd32c<0>(xa[j][0]);
-    sforc<144>([&](auto kc) {
+    for (int j = 0; j < NBLK; ++j) b0[j] = lds_rd32<0>(xa[j][0]);
+    static_for<144>([&](auto kc) {
       constexpr int k = kc, tap = k / 16, kk = k % 16;
       float (&bc)[NBLK] = (k & 1) ? b1 : b0;
       float (&bn)[NBLK] = (k & 1) ? b0 : b1;
-      sforc<NBLK>([&](auto jc) {
+      static_for<NBLK>([&](auto jc) {
         constexpr int j = jc;
         if constexpr (k + 1 < 144) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(bc[j]));
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bc[j]));
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[tap][kk], bc[j], acc[j], 0, 0, 0);
+        acc[j] = mfma16(wreg[tap][kk], bc[j], acc[j]);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (k + 1 < 144) {
           constexpr int k1 = k + 1, tap1 = k1 / 16, kk1 = k1 % 16, r1 = tap1 / 3, s1 = tap1 % 3;
           constexpr int off = (s1 * PS + 4 * kk1) * 4;
-          bn[j] = rd32c<off>(xa[j][r1]);
+          bn[j] = lds_rd32<off>(xa[j][r1]);
           __builtin_amdgcn_sched_barrier(0);
         }
       });

@@ -8,7 +8,7 @@
 // wave per SIMD -- while the workgroup walks its run of (image, 4-row strip) tiles; at the end every workgroup leaves a [64][3][3][64]
 // fp32 partial and rp_conv3x3_c64_wgrad's second launch sums the partials in a fixed order (deterministic, no atomics) into bf16.
 //   * both MFMA operands contract over PIXELS but lie pixel-major in memory (NHWC), so both are read with the LDS transpose read
-//     (ds_read_b64_tr_b16: 4 pixels x 16 channels per 16-lane group -> a lane holds 4 consecutive pixels of its own channel); two
+//     (tr_read of bf16_path.h: 4 pixels x 16 channels per 16-lane group -> a lane holds 4 consecutive pixels of its own channel); two
 //     reads = one bf16x8 operand of v_mfma_f32_32x32x16_bf16;
 //   * LDS images in PLANES, one per 16-byte channel chunk ([chunk][position][16 B], plane stride = 64 B mod 256 B): the 32 lanes of a
 //     read's service group touch 4 planes x 4 consecutive positions = 4 x 64 B that tile the 256-byte bank row, and the address is
@@ -18,13 +18,11 @@
 //     outside the image for free) and land in the other LDS buffers piece by piece between the MFMAs: one barrier per tile;
 //   * per 16-pixel k-step a wave issues 2 + 9 x 2 transpose reads for 9 MFMAs, operands two MFMAs ahead (hand-placed reads and
 //     waits, conv3x3_bf16.hip explains why).
-#include <type_traits>
-#include "common.h"
+#include "bf16_path.h"
 #include "../../include/relpose_hip.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 constexpr int C = 64, IW = 56, IH = 56, TH = 4, TPI = IH / TH, HC = IW + 2, HR = TH + 2;
 constexpr int NPOS = HC * HR;                  // 348 halo positions
 constexpr int XPLANE = 356 * 16;               // 5696 B = 64 (mod 256)
@@ -46,27 +44,6 @@ struct WgP {
   int ntiles;
 };
 
-template <int I, int N, class F>
-RP_DEV void static_for_w(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for_w<I + 1, N>(f);
-  }
-}
-template <int IMM>
-RP_DEV void tr_read(unsigned long long& d, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(IMM));
-}
-template <int N>
-RP_DEV void lds_wait2(unsigned long long& a, unsigned long long& b, unsigned long long& c, unsigned long long& d) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
-}
-RP_DEV bf16x8 op8(unsigned long long lo, unsigned long long hi) {
-  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-  u64x2 v;
-  v[0] = lo; v[1] = hi;
-  return __builtin_bit_cast(bf16x8, v);
-}
 constexpr int reads_of(int step) { return step < 0 || step >= NSTEP ? 0 : 2 + (step % 9 == 0 ? 2 : 0); }
 
 __global__ __launch_bounds__(256, 1) void conv3x3_c64_wgrad_kernel(WgP p) {
@@ -136,11 +113,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_wgrad_kernel(WgP p) {
     issue(std::integral_constant<int, 1>{});
     const int tn2 = min(t + 2, t1 - 1);
     const bool more2 = t + 2 < t1;
-    static_for_w<0, NSTEP>([&](auto stc) {
+    static_for<NSTEP>([&](auto stc) {
       constexpr int st = decltype(stc)::value;
       if constexpr (st + 2 < NSTEP) issue(std::integral_constant<int, st + 2>{});
       constexpr int kk = st / 9, tap = st % 9;
-      lds_wait2<reads_of(st + 1) + reads_of(st + 2)>(A[kk & 1][0], A[kk & 1][1], B[st % 3][0], B[st % 3][1]);
+      tr_wait<reads_of(st + 1) + reads_of(st + 2)>(A[kk & 1][0], A[kk & 1][1], B[st % 3][0], B[st % 3][1]);
       acc[tap] = mfma_bf(op8(A[kk & 1][0], A[kk & 1][1]), op8(B[st % 3][0], B[st % 3][1]), acc[tap]);
       // between the MFMAs: the next tile's operands registers -> LDS (other buffers), the tile after that requested into the registers
       if constexpr (st % 7 == 3) {

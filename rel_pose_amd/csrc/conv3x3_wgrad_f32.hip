@@ -15,7 +15,6 @@
 //   * per 2-pixel k-step a wave issues 1 + 9 ds_read_b32 (immediate offsets: next to fp32 MFMAs LDS instructions are free, VALU
 //     instructions are not -- profiles/r5_shadow_lab.txt) for 9 MFMAs, operands one step ahead, waits written out by hand; the next
 //     tile's DMA pieces go out one per two k-steps behind the MFMAs.
-#include <type_traits>
 #include "common.h"
 #include "../../include/relpose_hip.h"
 
@@ -35,28 +34,6 @@ struct WgF {
   int ntiles;           // N * 56 image rows
 };
 
-RP_DEV void glds16r(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(lds_byte_addr), "s"(sbase) : "memory");
-}
-RP_DEV const void* uniform_ptr_r(const void* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
-template <int OFF> RP_DEV float rd32(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-template <int N, class F> RP_DEV void sfor(F&& f) {
-  if constexpr (N > 0) {
-    sfor<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
-
 __global__ __launch_bounds__(256, 1) void conv3x3_c64_wgrad_f32_kernel(WgF p) {
   __shared__ __attribute__((aligned(16))) float Xr[5][XROW];      // 74 240 B: ring slots 0 .. 3, slot 4 = a row of zeros
   __shared__ __attribute__((aligned(16))) float Ys[2][YROW];      // 28 672 B
@@ -72,13 +49,13 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_wgrad_f32_kernel(WgF p) {
 #pragma unroll
   for (int t = 0; t < 9; ++t) acc[t] = zero16();
 
-  const unsigned xs0 = (unsigned)(size_t)(rp_lds_ptr_t)(&Xr[0][0]), ys0 = (unsigned)(size_t)(rp_lds_ptr_t)(&Ys[0][0]);
+  const unsigned xs0 = lds_byte_addr(&Xr[0][0]), ys0 = lds_byte_addr(&Ys[0][0]);
   // DMA piece q (0 .. 13) of image row `row` of x into its ring slot / of dY into its buffer; pieces of a row are spread over the waves
   auto dma_x = [&](int row, int q) {
-    glds16r(uniform_ptr_r(p.x + (long long)row * YROW), (unsigned)(q * 1024 + lane * 16), xs0 + (row & 3) * (XROW * 4) + C * 4 + q * 1024);
+    glds16(uniform_ptr(p.x + (long long)row * YROW), (unsigned)(q * 1024 + lane * 16), xs0 + (row & 3) * (XROW * 4) + C * 4 + q * 1024);
   };
   auto dma_y = [&](int row, int q) {
-    glds16r(uniform_ptr_r(p.dy + (long long)row * YROW), (unsigned)(q * 1024 + lane * 16), ys0 + (row & 1) * (YROW * 4) + q * 1024);
+    glds16(uniform_ptr(p.dy + (long long)row * YROW), (unsigned)(q * 1024 + lane * 16), ys0 + (row & 1) * (YROW * 4) + q * 1024);
   };
   if (t0 < t1) {
     const int y0 = t0 % IH;
@@ -103,21 +80,21 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_wgrad_f32_kernel(WgF p) {
     const unsigned xa0 = xs0 + (top ? ((t - 1) & 3) : 4) * (XROW * 4) + xoff, xa1 = xs0 + (t & 3) * (XROW * 4) + xoff;
     const unsigned xa2 = xs0 + (bot ? ((t + 1) & 3) : 4) * (XROW * 4) + xoff;
     float a, bq[9];
-    a = rd32<0>(ya);
-    bq[0] = rd32<0>(xa0); bq[1] = rd32<C * 4>(xa0); bq[2] = rd32<2 * C * 4>(xa0);
-    bq[3] = rd32<0>(xa1); bq[4] = rd32<C * 4>(xa1); bq[5] = rd32<2 * C * 4>(xa1);
-    bq[6] = rd32<0>(xa2); bq[7] = rd32<C * 4>(xa2); bq[8] = rd32<2 * C * 4>(xa2);
-    sfor<KS>([&](auto kc) {
+    a = lds_rd32<0>(ya);
+    bq[0] = lds_rd32<0>(xa0); bq[1] = lds_rd32<C * 4>(xa0); bq[2] = lds_rd32<2 * C * 4>(xa0);
+    bq[3] = lds_rd32<0>(xa1); bq[4] = lds_rd32<C * 4>(xa1); bq[5] = lds_rd32<2 * C * 4>(xa1);
+    bq[6] = lds_rd32<0>(xa2); bq[7] = lds_rd32<C * 4>(xa2); bq[8] = lds_rd32<2 * C * 4>(xa2);
+    static_for<KS>([&](auto kc) {
       constexpr int k = kc;
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]), "+v"(bq[6]),
                    "+v"(bq[7]), "+v"(bq[8]));
       float an = 0.f, bn[9] = {};
       if constexpr (k + 1 < KS) {
         constexpr int o = 2 * (k + 1) * C * 4;
-        an = rd32<o>(ya);
-        bn[0] = rd32<o>(xa0); bn[1] = rd32<o + C * 4>(xa0); bn[2] = rd32<o + 2 * C * 4>(xa0);
-        bn[3] = rd32<o>(xa1); bn[4] = rd32<o + C * 4>(xa1); bn[5] = rd32<o + 2 * C * 4>(xa1);
-        bn[6] = rd32<o>(xa2); bn[7] = rd32<o + C * 4>(xa2); bn[8] = rd32<o + 2 * C * 4>(xa2);
+        an = lds_rd32<o>(ya);
+        bn[0] = lds_rd32<o>(xa0); bn[1] = lds_rd32<o + C * 4>(xa0); bn[2] = lds_rd32<o + 2 * C * 4>(xa0);
+        bn[3] = lds_rd32<o>(xa1); bn[4] = lds_rd32<o + C * 4>(xa1); bn[5] = lds_rd32<o + 2 * C * 4>(xa1);
+        bn[6] = lds_rd32<o>(xa2); bn[7] = lds_rd32<o + C * 4>(xa2); bn[8] = lds_rd32<o + 2 * C * 4>(xa2);
       }
       if constexpr (k % 2 == 0 && k < 16) {            // the next tile's rows: one DMA piece per two k-steps, behind the MFMAs
         constexpr int j = k / 2, q4 = 4 * (j & 3);

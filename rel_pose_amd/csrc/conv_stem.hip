@@ -15,9 +15,6 @@
 
 namespace {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-RP_DEV f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 constexpr int CO = 64, KH = 7, KW = 7, CI = 3, KROW = 24, KP = 176, NT_ = 11;     // 7 rows x 24 = 168, padded to 11 groups of 16
 constexpr int WROW = 192;                                                          // LDS row pitch (floats): 48 chunks of 16 bytes
 
@@ -150,13 +147,7 @@ __global__ __launch_bounds__(SNT, 4) void conv_stem_fwd_kernel(StemP p) {
 // per channel (the BatchNorm batch statistics come out of the convolution's epilogue: rp_bn_stats_from_partials finishes them)
 static int stem_slots() {
   static int slots = 0;
-  if (!slots) {
-    int dev = 0, cus = 256, per_cu = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_stem_fwd_kernel, SNT, 0);
-    slots = cus * (per_cu > 0 ? per_cu : 1);
-  }
+  if (!slots) slots = resident_slots<conv_stem_fwd_kernel, SNT>();
   return slots;
 }
 

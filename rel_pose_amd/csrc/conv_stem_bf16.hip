@@ -13,8 +13,6 @@
 
 namespace {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned short bf16_t;
 constexpr int CO = 64, KH = 7, KW = 7, CI = 3, KROW = 24, KT = 6;     // 7 filter rows x 24 = 168 taps, padded to 6 k-steps of 32
 constexpr int WPITCH = 256;                                            // LDS row pitch in bf16 elements (512 B = 32 chunks)
 constexpr int SNW = 8, SNT = SNW * 64;
@@ -77,7 +75,7 @@ __global__ __launch_bounds__(SNT, 4) void conv_stem_bf16_kernel(StemBP p) {
 #pragma unroll
       for (int hb = 0; hb < 4; ++hb) {
         const bf16x8 a = *reinterpret_cast<const bf16x8*>(wl + (16 * hb + j) * WPITCH + (((4 * t + q) ^ j) << 3));
-        acc[hb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pb[t], acc[hb], 0, 0, 0);
+        acc[hb] = mfma16bf(a, pb[t], acc[hb]);
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);          // one filter fragment in flight per MFMA (else all 24 are hoisted: 96 registers)
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       }
@@ -129,13 +127,7 @@ __global__ __launch_bounds__(SNT, 4) void conv_stem_bf16_kernel(StemBP p) {
 
 int stem_bf16_slots() {
   static int slots = 0;
-  if (!slots) {
-    int dev = 0, cus = 256, per_cu = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_stem_bf16_kernel<true>, SNT, 0);
-    slots = cus * (per_cu > 0 ? per_cu : 1);
-  }
+  if (!slots) slots = resident_slots<conv_stem_bf16_kernel<true>, SNT>();
   return slots;
 }
 

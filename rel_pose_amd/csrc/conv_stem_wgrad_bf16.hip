@@ -13,13 +13,11 @@
 //      16 pixels, both MFMA operands come from LDS by transpose reads (dY from 16-byte channel planes; P rows are copied as they lie:
 //      a position is 32 bytes, so the 4 x 16 block of a read is 128 contiguous bytes), next tile requested a tile ahead, one barrier per
 //      tile, fixed-order reduce of the per-workgroup partials (second launch) straight into the fp32 [64][7][7][3] gradient.
-#include <type_traits>
-#include "common.h"
+#include "bf16_path.h"
 #include "../../include/relpose_hip.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 constexpr int CO = 64, OW = 112, OH = 112, TH = 2, TPI = OH / TH;        // 56 strips of 2 output rows per image
 constexpr int PW = 115, PH = 115, PCH = 16;                               // space-to-depth image
 constexpr int XROWS = TH + 3, XPOS = XROWS * PW;                          // 5 rows x 115 positions of 32 B
@@ -41,27 +39,6 @@ struct SwP {
   int ntiles, N;
 };
 
-template <int I, int N, class F>
-RP_DEV void static_for_s(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for_s<I + 1, N>(f);
-  }
-}
-template <int IMM>
-RP_DEV void tr_read_s(unsigned long long& d, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(IMM));
-}
-template <int N>
-RP_DEV void lds_wait_s(unsigned long long& a, unsigned long long& b, unsigned long long& c, unsigned long long& d) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
-}
-RP_DEV bf16x8 op8s(unsigned long long lo, unsigned long long hi) {
-  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-  u64x2 v;
-  v[0] = lo; v[1] = hi;
-  return __builtin_bit_cast(bf16x8, v);
-}
 constexpr int reads_of_s(int step) { return step < 0 || step >= NSTEP ? 0 : 2 + (step % 4 == 0 ? 2 : 0); }
 
 __global__ __launch_bounds__(256, 1) void conv_stem_wgrad_kernel(SwP p) {
@@ -110,23 +87,23 @@ __global__ __launch_bounds__(256, 1) void conv_stem_wgrad_kernel(SwP p) {
       constexpr int st = decltype(stc)::value;
       constexpr int kk = st / 4, i = st % 4, u = i >> 1, v = 2 * (i & 1), ty = (16 * kk) / OW;
       if constexpr (i == 0) {
-        tr_read_s<BI * YBUF + (16 * kk) * 16>(A[kk & 1][0], aA);
-        tr_read_s<BI * YBUF + (16 * kk + 4) * 16>(A[kk & 1][1], aA);
+        tr_read<BI * YBUF + (16 * kk) * 16>(A[kk & 1][0], aA);
+        tr_read<BI * YBUF + (16 * kk + 4) * 16>(A[kk & 1][1], aA);
       }
       constexpr int imm = BI * XBUF + (16 * kk + 3 * ty + u * PW + v) * 32;
-      tr_read_s<imm>(B[st % 3][0], aBq);
-      tr_read_s<imm + 4 * 32>(B[st % 3][1], aBq);
+      tr_read<imm>(B[st % 3][0], aBq);
+      tr_read<imm + 4 * 32>(B[st % 3][1], aBq);
     };
     issue(std::integral_constant<int, 0>{});
     issue(std::integral_constant<int, 1>{});
     const int tn2 = min(t + 2, t1 - 1);
     const bool more2 = t + 2 < t1;
-    static_for_s<0, NSTEP>([&](auto stc) {
+    static_for<NSTEP>([&](auto stc) {
       constexpr int st = decltype(stc)::value;
       if constexpr (st + 2 < NSTEP) issue(std::integral_constant<int, st + 2>{});
       constexpr int kk = st / 4, i = st % 4;
-      lds_wait_s<reads_of_s(st + 1) + reads_of_s(st + 2)>(A[kk & 1][0], A[kk & 1][1], B[st % 3][0], B[st % 3][1]);
-      acc[i] = mfma_bf(op8s(A[kk & 1][0], A[kk & 1][1]), op8s(B[st % 3][0], B[st % 3][1]), acc[i]);
+      tr_wait<reads_of_s(st + 1) + reads_of_s(st + 2)>(A[kk & 1][0], A[kk & 1][1], B[st % 3][0], B[st % 3][1]);
+      acc[i] = mfma_bf(op8(A[kk & 1][0], A[kk & 1][1]), op8(B[st % 3][0], B[st % 3][1]), acc[i]);
       if constexpr (st % 4 == 2) {
         constexpr int pc = st / 4;
         if constexpr (pc < XV) {

@@ -13,7 +13,6 @@
 //      the MFMAs; an MFMA operand is one conflict-free ds_read_b32 with an immediate offset (lane = output channel / column, half-wave =
 //      which pixel of the k-step; a column's (tap, channel) offset sits in the lane's base address); per-workgroup partials, fixed-order
 //      reduce straight into the fp32 [64][7][7][3] gradient.
-#include <type_traits>
 #include "common.h"
 #include "../../include/relpose_hip.h"
 
@@ -36,28 +35,6 @@ struct SwF {
   int ntiles;           // N * 112 output rows
 };
 
-RP_DEV void glds16s(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(lds_byte_addr), "s"(sbase) : "memory");
-}
-RP_DEV const void* uniform_ptr_s(const void* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
-template <int OFF> RP_DEV float rd32s(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-template <int N, class F> RP_DEV void sfor_s(F&& f) {
-  if constexpr (N > 0) {
-    sfor_s<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
-
 __global__ __launch_bounds__(256, 1) void conv_stem_wgrad_f32_kernel(SwF p) {
   __shared__ __attribute__((aligned(16))) unsigned char Xs[2][XB];        // 45 056 B
   __shared__ __attribute__((aligned(16))) unsigned char Ys[2][YROWB];     // 57 344 B
@@ -65,7 +42,7 @@ __global__ __launch_bounds__(256, 1) void conv_stem_wgrad_f32_kernel(SwF p) {
   const int coh = wave >> 1, nq = wave & 1;
   const int G = gridDim.x, b = blockIdx.x;
   const int t0 = (int)((long long)p.ntiles * b / G), t1 = (int)((long long)p.ntiles * (b + 1) / G);
-  const unsigned xs0 = (unsigned)(size_t)(rp_lds_ptr_t)(&Xs[0][0]), ys0 = (unsigned)(size_t)(rp_lds_ptr_t)(&Ys[0][0]);
+  const unsigned xs0 = lds_byte_addr(&Xs[0][0]), ys0 = lds_byte_addr(&Ys[0][0]);
 
   f32x16 acc[3] = {zero16(), zero16(), zero16()};
   // column c = 32 (3 nq + i) + l31 = 12 tap + ch, tap = 4 u + v: P position (oy + u, ox + v), channel ch
@@ -79,11 +56,11 @@ __global__ __launch_bounds__(256, 1) void conv_stem_wgrad_f32_kernel(SwF p) {
 
   auto dma_x = [&](int t, int buf, int q) {   // piece q of the four P rows of tile t = (image t / 112, output row t % 112): one contiguous run
     const int img = t / OH, oy = t - img * OH;
-    glds16s(uniform_ptr_s(reinterpret_cast<const unsigned char*>(p.p) + ((long long)img * PH + oy) * PROWB), (unsigned)(q * 1024 + lane * 16),
+    glds16(uniform_ptr(reinterpret_cast<const unsigned char*>(p.p) + ((long long)img * PH + oy) * PROWB), (unsigned)(q * 1024 + lane * 16),
             xs0 + buf * XB + q * 1024);
   };
   auto dma_y = [&](int t, int buf, int q) {
-    glds16s(uniform_ptr_s(reinterpret_cast<const unsigned char*>(p.dy) + (long long)t * YROWB), (unsigned)(q * 1024 + lane * 16),
+    glds16(uniform_ptr(reinterpret_cast<const unsigned char*>(p.dy) + (long long)t * YROWB), (unsigned)(q * 1024 + lane * 16),
             ys0 + buf * YROWB + q * 1024);
   };
   if (t0 < t1) {
@@ -100,17 +77,17 @@ __global__ __launch_bounds__(256, 1) void conv_stem_wgrad_f32_kernel(SwF p) {
     const unsigned x0 = xs0 + (t & 1) * XB;
     const unsigned xa0 = x0 + boff[0], xa1 = x0 + boff[1], xa2 = x0 + boff[2];
     float a, b0, b1, b2;
-    a = rd32s<0>(ya);
-    b0 = rd32s<0>(xa0); b1 = rd32s<0>(xa1); b2 = rd32s<0>(xa2);
-    sfor_s<KS>([&](auto kc) {
+    a = lds_rd32<0>(ya);
+    b0 = lds_rd32<0>(xa0); b1 = lds_rd32<0>(xa1); b2 = lds_rd32<0>(xa2);
+    static_for<KS>([&](auto kc) {
       constexpr int k = kc;
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b0), "+v"(b1), "+v"(b2));
       float an = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f;
       if constexpr (k + 1 < KS) {
-        an = rd32s<2 * (k + 1) * CO * 4>(ya);
-        n0 = rd32s<2 * (k + 1) * PC * 4>(xa0);
-        n1 = rd32s<2 * (k + 1) * PC * 4>(xa1);
-        n2 = rd32s<2 * (k + 1) * PC * 4>(xa2);
+        an = lds_rd32<2 * (k + 1) * CO * 4>(ya);
+        n0 = lds_rd32<2 * (k + 1) * PC * 4>(xa0);
+        n1 = lds_rd32<2 * (k + 1) * PC * 4>(xa1);
+        n2 = lds_rd32<2 * (k + 1) * PC * 4>(xa2);
       }
       if constexpr (k % 4 == 0) {                      // the next tile: one DMA piece per four k-steps, behind the MFMAs
         constexpr int j = k / 4;                       // 0 .. 13

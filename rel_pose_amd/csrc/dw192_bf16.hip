@@ -10,38 +10,16 @@
 //     256 workgroups = one per CU) and keeps it in registers (4 waves x 3 x 3 accumulator tiles = 144 VGPRs);
 //   * 64-row stages of A and B go global -> LDS by LDS-DMA (16 bytes per lane) into two buffers; an fp32 B (the residual-stream
 //     gradients are fp32) is staged through registers instead and rounded to bf16 once per stage;
-//   * every MFMA operand is two ds_read_b64_tr_b16 (lane = output row / column, 8 consecutive tokens per lane), 12 reads per 9 MFMAs;
+//   * every MFMA operand is two LDS transpose reads (tr_operand of bf16_path.h; lane = output row / column, 8 consecutive tokens per
+//     lane), 12 reads per 9 MFMAs;
 //     rows are 24 chunks of 16 bytes, chunk ^ (((row >> 1) & 1) << 2) puts the four rows of a transpose-read block into four
 //     different 64-byte quarters of the bank row;
 //   * partial tiles are written as split-K slabs in rp_gemm's workspace layout ([split][N][192] fp32) and finished by the same
 //     fixed-order reduce (rp_splitk_reduce_multi, optionally transposing): deterministic, no atomics.
-#include "common.h"
+#include "bf16_path.h"
 #include "../../include/relpose_hip.h"
 
 namespace {
-
-typedef unsigned short bf16_t;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-RP_DEV void glds16w(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(lds_byte_addr), "s"(sbase) : "memory");
-}
-RP_DEV const void* uniform_vp(const void* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
-RP_DEV bf16x8 tr_op(const bf16_t* a0, const bf16_t* a1) {
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)a0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)a1);
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3]; v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 constexpr int W = 192;            // tile extent both ways
 constexpr int SR = 64;            // token rows per stage
@@ -51,8 +29,6 @@ struct DwP {
   const bf16_t* a; const void* b; float* ws;
   int M, N, lda, rows_per_split, nsplit;
 };
-
-RP_DEV int swz_w(int r) { return ((r >> 1) & 1) << 2; }
 
 template <bool BF32>
 __global__ __launch_bounds__(256, 1) void dw192_bf16_kernel(DwP p) {
@@ -80,20 +56,20 @@ __global__ __launch_bounds__(256, 1) void dw192_bf16_kernel(DwP p) {
   for (int i = 0; i < 6; ++i) {
     const int byte = (wave + 4 * i) * 1024 + lane * 16;
     const int r = byte / 384, slot = (byte % 384) >> 4;
-    const int ch = slot ^ swz_w(r);
+    const int ch = slot ^ swz_v(r);
     aoff[i] = (unsigned)(r * p.lda + ch * 8) * 2u;
     boff[i] = (unsigned)(r * W + ch * 8) * 2u;
   }
-  const unsigned as0 = (unsigned)(size_t)(rp_lds_ptr_t)(&As[0][0]) + wave * 1024, bs0 = (unsigned)(size_t)(rp_lds_ptr_t)(&Bs[0][0]) + wave * 1024;
+  const unsigned as0 = lds_byte_addr(&As[0][0]) + wave * 1024, bs0 = lds_byte_addr(&Bs[0][0]) + wave * 1024;
   auto issue_a = [&](int s, int buf) {
-    const void* src = uniform_vp(ab + (long long)s * SR * p.lda);
+    const void* src = uniform_ptr(ab + (long long)s * SR * p.lda);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) glds16w(src, aoff[i], as0 + buf * (ST_EL * 2) + i * 4096);
+    for (int i = 0; i < 6; ++i) glds16(src, aoff[i], as0 + buf * (ST_EL * 2) + i * 4096);
   };
   auto issue_b = [&](int s, int buf) {
-    const void* src = uniform_vp(bb16 + (long long)s * SR * W);
+    const void* src = uniform_ptr(bb16 + (long long)s * SR * W);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) glds16w(src, boff[i], bs0 + buf * (ST_EL * 2) + i * 4096);
+    for (int i = 0; i < 6; ++i) glds16(src, boff[i], bs0 + buf * (ST_EL * 2) + i * 4096);
   };
   // fp32 B: thread t takes float4 number t + 256 i (i = 0..11) of the [64][192] fp32 stage = row (t + 256 i) / 48, columns 4 ((t + 256 i) % 48)
   float4 breg[BF32 ? 12 : 1];
@@ -106,7 +82,7 @@ __global__ __launch_bounds__(256, 1) void dw192_bf16_kernel(DwP p) {
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
       const int f = tid + 256 * i, r = f / 48, c4 = f % 48;            // 4 elements = half a chunk
-      const int slot = (c4 >> 1) ^ swz_w(r);
+      const int slot = (c4 >> 1) ^ swz_v(r);
       *reinterpret_cast<uint2*>(&Bs[buf][0] + r * W + slot * 8 + 4 * (c4 & 1)) =
           make_uint2(pk_bf16(breg[i].x, breg[i].y), pk_bf16(breg[i].z, breg[i].w));
     }
@@ -139,8 +115,8 @@ __global__ __launch_bounds__(256, 1) void dw192_bf16_kernel(DwP p) {
       bf16x8 af[3], bfr[3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        af[i] = tr_op(At + st * 16 * W + aofs[i], At + st * 16 * W + 4 * W + aofs[i]);
-        bfr[i] = tr_op(Bt + st * 16 * W + bofs[i], Bt + st * 16 * W + 4 * W + bofs[i]);
+        af[i] = tr_operand(At + st * 16 * W + aofs[i], At + st * 16 * W + 4 * W + aofs[i]);
+        bfr[i] = tr_operand(Bt + st * 16 * W + bofs[i], Bt + st * 16 * W + 4 * W + bofs[i]);
       }
 #pragma unroll
       for (int i = 0; i < 3; ++i)

@@ -13,33 +13,10 @@
 //   * per 2-row k-step a wave issues 6 ds_read_b32 for 9 MFMAs (576 matrix-pipe cycles): LDS and issue bandwidth are idle, one barrier
 //     per 144 MFMAs;
 //   * split-K slabs in rp_gemm's workspace layout, finished by the same fixed-order reduce (rp_splitk_reduce_multi): deterministic.
-#include <type_traits>
 #include "common.h"
 #include "../../include/relpose_hip.h"
 
 namespace {
-
-RP_DEV void glds16f(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(lds_byte_addr), "s"(sbase) : "memory");
-}
-template <int OFF> RP_DEV float lds_rd32(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-template <int N, class F> RP_DEV void static_for(F&& f) {
-  if constexpr (N > 0) {
-    static_for<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
-RP_DEV const void* uniform_vpf(const void* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
 
 constexpr int W = 192;            // tile extent both ways
 constexpr int SR = 32;            // token rows per stage
@@ -73,14 +50,14 @@ __global__ __launch_bounds__(256, 1) void dw192_f32_kernel(DwF p) {
     aoff[i] = (unsigned)(r * p.lda * 4 + c);
     boff[i] = (unsigned)(r * W * 4 + c);
   }
-  const unsigned as0 = (unsigned)(size_t)(rp_lds_ptr_t)(&As[0][0]) + wave * 1024, bs0 = (unsigned)(size_t)(rp_lds_ptr_t)(&Bs[0][0]) + wave * 1024;
+  const unsigned as0 = lds_byte_addr(&As[0][0]) + wave * 1024, bs0 = lds_byte_addr(&Bs[0][0]) + wave * 1024;
   auto issue = [&](int s, int buf) {
-    const void* sa = uniform_vpf(ab + (long long)s * SR * p.lda);
-    const void* sb = uniform_vpf(bb + (long long)s * SR * W);
+    const void* sa = uniform_ptr(ab + (long long)s * SR * p.lda);
+    const void* sb = uniform_ptr(bb + (long long)s * SR * W);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) glds16f(sa, aoff[i], as0 + buf * (ST_FL * 4) + i * 4096);
+    for (int i = 0; i < 6; ++i) glds16(sa, aoff[i], as0 + buf * (ST_FL * 4) + i * 4096);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) glds16f(sb, boff[i], bs0 + buf * (ST_FL * 4) + i * 4096);
+    for (int i = 0; i < 6; ++i) glds16(sb, boff[i], bs0 + buf * (ST_FL * 4) + i * 4096);
   };
 
   const int wr = wave >> 1, wc = wave & 1;                           // this wave's 96 x 96 quadrant of the tile
@@ -100,15 +77,15 @@ __global__ __launch_bounds__(256, 1) void dw192_f32_kernel(DwF p) {
     // issued as a block at the stage's top they held the in-order wave -- and the idle pipe -- for ~7 % of the launch
     // (tools/lab/dw_ablate.sh, profiles/r5_dw_ablate.txt).  The last stage re-fetches itself into the dead buffer (no branch in the loop).
     const int sn = min(s + 1, nst - 1);
-    const void* sa = uniform_vpf(ab + (long long)sn * SR * p.lda);
-    const void* sb = uniform_vpf(bb + (long long)sn * SR * W);
+    const void* sa = uniform_ptr(ab + (long long)sn * SR * p.lda);
+    const void* sb = uniform_ptr(bb + (long long)sn * SR * W);
     const unsigned an0 = as0 + (buf ^ 1) * (ST_FL * 4), bn0 = bs0 + (buf ^ 1) * (ST_FL * 4);
     // Operands of k-step t + 1 are read while the nine MFMAs of step t run (one wave per SIMD: nobody else hides the LDS latency), as
     // ds_read_b32 with the step's offset as an IMMEDIATE: hipcc's ds_read2_b32 pairs need a fresh base register per step (8-bit offsets),
     // 32 v_add_u32 per stage, and next to an fp32 MFMA a VALU instruction costs its issue time while an LDS instruction is free
     // (profiles/r5_shadow_lab.txt).  The asm reads are invisible to the compiler's counters: the wait is written out, with the six
     // registers passed through it.
-    const unsigned at = (unsigned)(size_t)(rp_lds_ptr_t)(As[buf] + ao), bt = (unsigned)(size_t)(rp_lds_ptr_t)(Bs[buf] + bo);
+    const unsigned at = lds_byte_addr(As[buf] + ao), bt = lds_byte_addr(Bs[buf] + bo);
     float af[3], bf[3];
     static_for<3>([&](auto i) {
       af[i] = lds_rd32<128 * i>(at);
@@ -124,8 +101,8 @@ __global__ __launch_bounds__(256, 1) void dw192_f32_kernel(DwF p) {
           bn[i] = lds_rd32<(2 * (t + 1) * W + 32 * i) * 4>(bt);
         });
       }
-      if (t < 6) glds16f(sa, aoff[t < 6 ? t : 0], an0 + t * 4096);
-      else if (t < 12) glds16f(sb, boff[t >= 6 && t < 12 ? t - 6 : 0], bn0 + (t - 6) * 4096);
+      if (t < 6) glds16(sa, aoff[t < 6 ? t : 0], an0 + t * 4096);
+      else if (t < 12) glds16(sb, boff[t >= 6 && t < 12 ? t - 6 : 0], bn0 + (t - 6) * 4096);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < 3; ++i)

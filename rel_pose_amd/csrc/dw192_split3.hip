@@ -22,7 +22,6 @@
 //   * same split-K slabs / fixed-order reduce as rp_dw192_f32 (rp_dw192_f32_splits / _workspace_bytes apply): deterministic.
 // Not handled (documented, not needed for gradients): an Inf operand gives NaN (Inf - Inf in the split); limbs below the bf16 normal
 // range are flushed, i.e. elements below ~2^-108 lose their low limbs (absolute error < 2^-126 per product).
-#include <type_traits>
 #include "common.h"
 #include "../../include/relpose_hip.h"
 
@@ -30,17 +29,6 @@ namespace {
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-RP_DEV void glds16s(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(lds_byte_addr), "s"(sbase) : "memory");
-}
-RP_DEV const void* uniform_vps(const void* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
 
 constexpr int W = 192;            // tile extent both ways
 constexpr int SR = 32;            // token rows per stage (two 16-row MFMA steps)
@@ -134,16 +122,16 @@ __global__ __launch_bounds__(256, 1) void dw192_split3_kernel(DwS p) {
     aoff[i] = (unsigned)(r * p.lda * 4 + c);
     boff[i] = (unsigned)(r * W * 4 + c);
   }
-  const unsigned as0 = (unsigned)(size_t)(rp_lds_ptr_t)(&As[0][0]) + wave * 1024, bs0 = (unsigned)(size_t)(rp_lds_ptr_t)(&Bs[0][0]) + wave * 1024;
+  const unsigned as0 = lds_byte_addr(&As[0][0]) + wave * 1024, bs0 = lds_byte_addr(&Bs[0][0]) + wave * 1024;
   // stage s -> slot; stages past the end re-fetch the last one into a dead slot (no branch, constant vmcnt)
   auto issue = [&](int s, int slot) {
     const int sc = min(s, nst - 1);
-    const void* sa = uniform_vps(ab + (long long)sc * SR * p.lda);
-    const void* sb = uniform_vps(bb + (long long)sc * SR * W);
+    const void* sa = uniform_ptr(ab + (long long)sc * SR * p.lda);
+    const void* sb = uniform_ptr(bb + (long long)sc * SR * W);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) glds16s(sa, aoff[i], as0 + slot * (ST_FL * 4) + i * 4096);
+    for (int i = 0; i < 6; ++i) glds16(sa, aoff[i], as0 + slot * (ST_FL * 4) + i * 4096);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) glds16s(sb, boff[i], bs0 + slot * (ST_FL * 4) + i * 4096);
+    for (int i = 0; i < 6; ++i) glds16(sb, boff[i], bs0 + slot * (ST_FL * 4) + i * 4096);
   };
 
   const int wr = wave >> 1, wc = wave & 1;                           // this wave's 96 x 96 quadrant of the tile
@@ -193,8 +181,8 @@ __global__ __launch_bounds__(256, 1) void dw192_split3_kernel(DwS p) {
     }
     __builtin_amdgcn_sched_barrier(0);
     const int q = 6 * kk + g;
-    if (q < 6) glds16s(sa, aoff[q < 6 ? q : 0], adst + q * 4096);
-    else glds16s(sb, boff[q >= 6 ? q - 6 : 0], bdst + (q - 6) * 4096);
+    if (q < 6) glds16(sa, aoff[q < 6 ? q : 0], adst + q * 4096);
+    else glds16(sb, boff[q >= 6 ? q - 6 : 0], bdst + (q - 6) * 4096);
     __builtin_amdgcn_sched_barrier(0);
   };
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
@@ -223,8 +211,8 @@ __global__ __launch_bounds__(256, 1) void dw192_split3_kernel(DwS p) {
     asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     const int sc = min(s + 3, nst - 1);                               // (past the end: a re-fetch into a dead slot, constant vmcnt)
-    const void* sa = uniform_vps(ab + (long long)sc * SR * p.lda);
-    const void* sb = uniform_vps(bb + (long long)sc * SR * W);
+    const void* sa = uniform_ptr(ab + (long long)sc * SR * p.lda);
+    const void* sb = uniform_ptr(bb + (long long)sc * SR * W);
     const unsigned adst = as0 + slot * (ST_FL * 4), bdst = bs0 + slot * (ST_FL * 4);
     const float* at = As[nslot] + ao;
     const float* bt = Bs[nslot] + bo;

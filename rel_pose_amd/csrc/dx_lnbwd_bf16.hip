@@ -21,9 +21,6 @@
 namespace {
 using namespace bf16path;
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-RP_DEV f32x4v mfma16bf(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
 constexpr int C = 192;            // output width = LayerNorm width
 constexpr int NWV = 4;            // waves per workgroup: 64 rows per tile; three workgroups per CU run in different phases
 constexpr int ROWS = NWV * 16;
@@ -54,11 +51,11 @@ __global__ __launch_bounds__(NWV * 64, 3) void dx_lnbwd_bf16_kernel(DxP p) {
     const int u = (3 * wave + i) * 16 + (lane >> 2), slot = lane & 3;
     woff[i] = (unsigned)(u * p.K * 2 + ((slot ^ ((0 - (u >> 2)) & 3)) << 4));
   }
-  const unsigned ws0 = lds_addr_of(&Ws[0][0]) + wave * 3072;
+  const unsigned ws0 = lds_byte_addr(&Ws[0][0]) + wave * 3072;
   auto issue = [&](int c, int buf) {
-    const void* src = uniform_vptr(p.wt + c * 32);
+    const void* src = uniform_ptr(p.wt + c * 32);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) glds16b(src, woff[i], ws0 + buf * (CHUNK_EL * 2) + i * 1024);
+    for (int i = 0; i < 3; ++i) glds16(src, woff[i], ws0 + buf * (CHUNK_EL * 2) + i * 1024);
   };
   issue(0, 0);
   issue(1, 1);

@@ -14,14 +14,11 @@
 // rp_emm_finalize (rowwise.hip) -> deterministic.
 // rp_emm_grad is the gradient pass (see DESIGN.md "EMM backward" for the algebra):
 //     dA = W X^T,  dS = 2 A dA - R rho_i - C gamma_j,  d owner = scale * dS * other
-#include "common.h"
+#include "tile32.h"
 #include "../../include/relpose_hip.h"
 
 namespace {
 
-constexpr int NTOK = 576;
-constexpr int NTILE = NTOK / 32;
-constexpr int KST = 68;
 constexpr int XW = 96;      // padded width of X / T / W rows
 constexpr int NW = 3;       // waves per workgroup: 96 owner rows
 constexpr int NT = NW * 64;
@@ -40,54 +37,6 @@ struct EmmP {
                          // (the MFMA accumulator image of the tile), so the key-side gradient dk = scale dS^T q is one rp_ds_matmul
                          // instead of a second pass that recomputes S and dA
 };
-
-template <int NTH>
-RP_DEV void kv_gload(const float* base, int ld, int tid, float4 (&r)[(512 + NTH - 1) / NTH]) {
-#pragma unroll
-  for (int j = 0; j < (512 + NTH - 1) / NTH; ++j) {
-    const int f = min(tid + NTH * j, 511);     // surplus threads duplicate the last element (no exec-masked guard)
-    r[j] = ld4(base + (long long)(f >> 4) * ld + (f & 15) * 4);
-  }
-}
-template <int NTH>
-RP_DEV void kv_sstore(float* s, int tid, const float4 (&r)[(512 + NTH - 1) / NTH]) {
-#pragma unroll
-  for (int j = 0; j < (512 + NTH - 1) / NTH; ++j) {
-    const int f = min(tid + NTH * j, 511);
-    st4(s + (f >> 4) * KST + (f & 15) * 4, r[j]);
-  }
-}
-
-template <bool BF>
-RP_DEV f32x16 score_tile(const float* Ks, int l31, int hi, const float (&breg)[32], const bf16x8 (&bpk)[4]) {
-  f32x16 s = zero16();
-  const float* kr = Ks + l31 * KST + 32 * hi;
-  if (BF) {      // bf16 operand mode (common.h): 8 consecutive k-steps of a lane = one v_mfma_f32_32x32x16_bf16
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float4 x = ld4(kr + 8 * c), y = ld4(kr + 8 * c + 4);
-      s = mfma_bf(pack8(x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w), bpk[c], s);
-    }
-    return s;
-  }
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float4 kf = ld4(kr + 4 * c);
-    s = mfma32(kf.x, breg[4 * c + 0], s);
-    s = mfma32(kf.y, breg[4 * c + 1], s);
-    s = mfma32(kf.z, breg[4 * c + 2], s);
-    s = mfma32(kf.w, breg[4 * c + 3], s);
-  }
-  return s;
-}
-
-RP_DEV void load_owner(const float* row_ptr, int hi, float mul, float (&reg)[32]) {
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float4 x = ld4(row_ptr + 32 * hi + 4 * c);
-    reg[4 * c + 0] = x.x * mul; reg[4 * c + 1] = x.y * mul; reg[4 * c + 2] = x.z * mul; reg[4 * c + 3] = x.w * mul;
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 template <bool BF>
@@ -132,13 +81,13 @@ __global__ __launch_bounds__(NT, 3) void emm_apply_kernel(EmmP p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) st4(s + (tid + NT * j) * 4, xpre[j]);
   };
-  kv_gload<NT>(lb, p.ld, tid, kpre);
+  tile_gload<NT>(lb, p.ld, tid, kpre);
   x_gload(0);
   // branch-free (every thread loads; lane & 31 picks the value): an exec-masked load here made hipcc wait vmcnt(0) -- for the tile
   // prefetch just issued -- at the top of every iteration (see attn_bwd_dkdv_kernel)
   const float* csrc = loop_lse + (tid & 31);
   cpre = csrc[0] * RP_LOG2E;
-  kv_sstore<NT>(Ks, tid, kpre);
+  tile_sstore<NT, KST>(Ks, tid, kpre);
   x_sstore(Xs);
   if (tid < 32) Cl[tid] = cpre;
   __syncthreads();
@@ -146,7 +95,7 @@ __global__ __launch_bounds__(NT, 3) void emm_apply_kernel(EmmP p) {
   for (int t = 0; t < NTILE; ++t) {
     const int cur = t & 1;
     if (t + 1 < NTILE) {
-      kv_gload<NT>(lb + (long long)(t + 1) * 32 * p.ld, p.ld, tid, kpre);
+      tile_gload<NT>(lb + (long long)(t + 1) * 32 * p.ld, p.ld, tid, kpre);
       x_gload(t + 1);
       cpre = csrc[(t + 1) * 32] * RP_LOG2E;
     }
@@ -184,7 +133,7 @@ __global__ __launch_bounds__(NT, 3) void emm_apply_kernel(EmmP p) {
     }
     }
     if (t + 1 < NTILE) {
-      kv_sstore<NT>(Ks + (cur ^ 1) * 32 * KST, tid, kpre);
+      tile_sstore<NT, KST>(Ks + (cur ^ 1) * 32 * KST, tid, kpre);
       x_sstore(Xs + (cur ^ 1) * 32 * XW);
       if (tid < 32) Cl[(cur ^ 1) * 32 + tid] = cpre;
     }
@@ -448,14 +397,16 @@ __global__ __launch_bounds__(GT, 2) void emm_grad_kernel(EmmP p) {
       st4(s + (f / 18) * XGS + (f % 18) * 4, xpre[j]);
     }
   };
-  kv_gload<GT>(lb, p.ld, tid, kpre);
+  // CLAMP = true at the four GT call sites: redundant (128 divides 512), kept so that no instruction changes -- hipcc does not prove it
+  // redundant and reschedules the kernel without it; removing it is a separate, measured change
+  tile_gload<GT, true>(lb, p.ld, tid, kpre);
   x_gload(0);
   const float* lsrc = (tid & 32) ? loop_g + (tid & 31) : loop_lse + (tid & 31);      // branch-free, see emm_apply_kernel
   const float lmul = (tid & 32) ? pre : RP_LOG2E;
   lpre = lsrc[0] * lmul;
   f32x16 sa = zero16(), sb = zero16();
   if (LS) sload(sa, 0);
-  kv_sstore<GT>(Ks[0], tid, kpre);
+  tile_sstore<GT, KST, true>(Ks[0], tid, kpre);
   x_sstore(Xs[0]);
   if (tid < 64) Ll[0][tid] = lpre;
   __syncthreads();
@@ -463,7 +414,7 @@ __global__ __launch_bounds__(GT, 2) void emm_grad_kernel(EmmP p) {
   auto step = [&](f32x16& s, f32x16& sn, int t) {
     const int cur = t & 1;
     if (t + 1 < NTILE) {
-      kv_gload<GT>(lb + (long long)(t + 1) * 32 * p.ld, p.ld, tid, kpre);
+      tile_gload<GT, true>(lb + (long long)(t + 1) * 32 * p.ld, p.ld, tid, kpre);
       x_gload(t + 1);
       lpre = lsrc[(t + 1) * 32] * lmul;
       if (LS) sload(sn, t + 1);
@@ -536,7 +487,7 @@ __global__ __launch_bounds__(GT, 2) void emm_grad_kernel(EmmP p) {
     }
     }
     if (t + 1 < NTILE) {
-      kv_sstore<GT>(Ks[cur ^ 1], tid, kpre);
+      tile_sstore<GT, KST, true>(Ks[cur ^ 1], tid, kpre);
       x_sstore(Xs[cur ^ 1]);
       if (tid < 64) Ll[cur ^ 1][tid] = lpre;
     }

@@ -6,7 +6,7 @@
 //     T = A X;  F = X^T T;      backward: W = X dF, W' = X dF^T, U = A^T X, rho = <W, T>, gamma = <W', U>,
 //     dX = T dF^T + U dF,  dA = W X^T,  dS = 2 A dA - R rho_i - C gamma_j,  dq = scale dS k,  dk = scale dS^T q.
 // Here q | k | v, X, T, U, W, W' live in HBM as bf16 and every contraction runs on v_mfma_f32_32x32x16_bf16 from LDS-DMA tiles and
-// ds_read_b128 / ds_read_b64_tr_b16 operands (bf16_path.h), fp32 accumulation; the normalisers (log2 units, from rp_attn_fwd_bf16's
+// ds_read_b128 / transpose-read operands (bf16_path.h), fp32 accumulation; the normalisers (log2 units, from rp_attn_fwd_bf16's
 // statistics form), rho, gamma and dF stay fp32.  The 576 x 576 matrices never exist: every pass recomputes S tile by tile.
 //   rp_emm_build_x_bf16   X from the bf16 qkv and the fp32 positional features
 //   rp_emm_apply_bf16     T = A X (owner = query rows) or U = A^T X (swap: owner = key rows), stored transposed-accumulated like
@@ -102,14 +102,14 @@ __global__ __launch_bounds__(NW * 64, 3) void emm_apply_bf16_kernel(EmmBfP p) {
   }
 #pragma unroll
   for (int i = 0; i < 3; ++i) xvoff[i] = (unsigned)((3 * wave + i) * 1024 + lane * 16);          // X rows are contiguous: a plain copy
-  const unsigned ls0 = lds_addr_of(&Ls[0][0]) + wave * 2048, xs0 = lds_addr_of(&Xs[0][0]) + wave * 3072;
+  const unsigned ls0 = lds_byte_addr(&Ls[0][0]) + wave * 2048, xs0 = lds_byte_addr(&Xs[0][0]) + wave * 3072;
   auto issue = [&](int s, int buf) {
-    const void* ll = uniform_vptr(lb + (long long)s * 32 * p.ld);
-    const void* xx = uniform_vptr(xb + (long long)s * 32 * XW);
-    glds16b(ll, lvoff[0], ls0 + buf * 4096);
-    glds16b(ll, lvoff[1], ls0 + buf * 4096 + 1024);
+    const void* ll = uniform_ptr(lb + (long long)s * 32 * p.ld);
+    const void* xx = uniform_ptr(xb + (long long)s * 32 * XW);
+    glds16(ll, lvoff[0], ls0 + buf * 4096);
+    glds16(ll, lvoff[1], ls0 + buf * 4096 + 1024);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) glds16b(xx, xvoff[i], xs0 + buf * 6144 + i * 1024);
+    for (int i = 0; i < 3; ++i) glds16(xx, xvoff[i], xs0 + buf * 6144 + i * 1024);
   };
   issue(0, 0);
 
@@ -173,14 +173,14 @@ __global__ __launch_bounds__(192, 2) void emm_f_bf16_kernel(const bf16_t* __rest
   const bf16_t* xb = x + zh * NTOK * XW;
   const bf16_t* tb = t + zh * NTOK * XW;
   // 64 rows x 192 B = 12 pieces per operand and stage, 4 per wave; plain copies (natural layout: 192-byte rows are skewed by themselves)
-  const unsigned xs0 = lds_addr_of(&Xs[0][0]) + wave * 4096, ts0 = lds_addr_of(&Ts[0][0]) + wave * 4096;
+  const unsigned xs0 = lds_byte_addr(&Xs[0][0]) + wave * 4096, ts0 = lds_byte_addr(&Ts[0][0]) + wave * 4096;
   auto issue = [&](int s, int buf) {
-    const void* xx = uniform_vptr(xb + (long long)s * 64 * XW);
-    const void* tt = uniform_vptr(tb + (long long)s * 64 * XW);
+    const void* xx = uniform_ptr(xb + (long long)s * 64 * XW);
+    const void* tt = uniform_ptr(tb + (long long)s * 64 * XW);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      glds16b(xx, (unsigned)((4 * wave + i) * 1024 + lane * 16), xs0 + buf * 12288 + i * 1024);
-      glds16b(tt, (unsigned)((4 * wave + i) * 1024 + lane * 16), ts0 + buf * 12288 + i * 1024);
+      glds16(xx, (unsigned)((4 * wave + i) * 1024 + lane * 16), xs0 + buf * 12288 + i * 1024);
+      glds16(tt, (unsigned)((4 * wave + i) * 1024 + lane * 16), ts0 + buf * 12288 + i * 1024);
     }
   };
   issue(0, 0);
@@ -341,14 +341,14 @@ __global__ __launch_bounds__(NW * 64, 3) void emm_grad_bf16_kernel(EmmBfP p) {
     const int byte = (3 * wave + i) * 1024 + lane * 16, r = byte / 192, slot = (byte % 192) >> 4;
     xvoff[i] = (unsigned)(r * 192 + ((slot ^ swz_x(r)) << 4));
   }
-  const unsigned ls0 = lds_addr_of(&Ls[0][0]) + wave * 2048, xs0 = lds_addr_of(&Xs[0][0]) + wave * 3072;
+  const unsigned ls0 = lds_byte_addr(&Ls[0][0]) + wave * 2048, xs0 = lds_byte_addr(&Xs[0][0]) + wave * 3072;
   auto issue = [&](int s, int buf) {
-    const void* ll = uniform_vptr(lb + (long long)s * 32 * p.ld);
-    const void* xx = uniform_vptr(xb + (long long)s * 32 * XW);
-    glds16b(ll, lvoff[0], ls0 + buf * 4096);
-    glds16b(ll, lvoff[1], ls0 + buf * 4096 + 1024);
+    const void* ll = uniform_ptr(lb + (long long)s * 32 * p.ld);
+    const void* xx = uniform_ptr(xb + (long long)s * 32 * XW);
+    glds16(ll, lvoff[0], ls0 + buf * 4096);
+    glds16(ll, lvoff[1], ls0 + buf * 4096 + 1024);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) glds16b(xx, xvoff[i], xs0 + buf * 6144 + i * 1024);
+    for (int i = 0; i < 3; ++i) glds16(xx, xvoff[i], xs0 + buf * 6144 + i * 1024);
   };
   issue(0, 0);
 

@@ -2,7 +2,7 @@
 //
 // Same tiling, operand layouts, k-step pairing, XCD-aware tile order, split-K and epilogue as gemm.hip's register-staged
 // kernel (which stays for the bf16-limb precisions and ragged K); what changes is how a k-tile reaches LDS:
-//   * global -> LDS directly (global_load_lds_dwordx4: 16 bytes per lane, 1 KB per wave instruction, no VGPR round trip and
+//   * global -> LDS directly (glds16 of common.h: 16 bytes per lane, 1 KB per wave instruction, no VGPR round trip and
 //     no ds_write pass), issued one k-tile ahead into the other of TWO LDS stages, so a k-iteration is
 //         issue DMA(kt+1) | 12 ds_read_b128 + 32 MFMA on stage kt | s_waitcnt vmcnt(0) ; s_barrier
 //     -- one barrier per k-tile instead of two, and the staging costs 6 issue slots per wave instead of 6 loads + 6 ds_write

@@ -19,8 +19,6 @@
 
 namespace {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-RP_DEV f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 // bf16 operand precision (BF = true, the bf16 configuration): v_mfma_f32_16x16x32_bf16.  Lane (j, q) of a 32-wide k block u supplies
 // the 8 CONSECUTIVE values k = 32 u + 8 q .. + 7 of its row: the weights arrive as bf16 (the host keeps a bf16 copy, refreshed when
 // the fp32 master changes), so a staged chunk is [32 units][192] bf16 = 12 KB (half the DMA and LDS traffic of the fp32 form) and
@@ -28,7 +26,6 @@ RP_DEV f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_
 // The accumulator layout, and so the whole epilogue, is that of the fp32 form.  LDS image of a chunk: 24 slots of 16 B per unit
 // row (384 B = 1.5 bank rows), slot index XOR-swizzled within its group of 8 by (row >> 1) & 7: the 16 lanes of a read then cover
 // 16 distinct 16-byte slots of the 256-byte bank row.
-RP_DEV f32x4v mfma16bf(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 constexpr int C = 192, CH = 32, WT = CH * C;               // 6144 floats = 24 KB per staged weight chunk
 constexpr int NW = 4, NT = NW * 64, ROWS = NW * 16, DMA = (WT / 4) / NT;   // 6 LDS-DMA rounds per chunk
@@ -362,13 +359,7 @@ __global__ __launch_bounds__(NT, 3) void linear_rows_kernel(RowsP p) {
 template <bool LN, bool BF>
 int rows_slots() {
   static int slots = 0;
-  if (!slots) {
-    int dev = 0, cus = 256, per_cu = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, linear_rows_kernel<LN, BF>, NT, 0);
-    slots = cus * (per_cu > 0 ? per_cu : 1);
-  }
+  if (!slots) slots = resident_slots<linear_rows_kernel<LN, BF>, NT>();
   return slots;
 }
 

@@ -16,7 +16,7 @@
 //                                                                 lane (j, q) is H[unit 4q + r][row j] = the B operand of k-step r,
 //                                                                 so the hidden activation never leaves the register file.
 // The contraction order inside a k-group is free, so both A operands are read as one ds_read_b128 per 4 k-steps.
-// Weights: W1 chunk [32 x 192] and W2 chunk [192 x 32] (24 KB each) are staged by LDS-DMA (global_load_lds_dwordx4, lane-linear
+// Weights: W1 chunk [32 x 192] and W2 chunk [192 x 32] (24 KB each) are staged by LDS-DMA (glds16 of common.h, lane-linear
 // -> unpadded tiles, XOR-swizzled 16-byte chunks so that the 16 rows one read group touches fall into 16 distinct bank groups);
 // single-buffered, two barriers per chunk: W2(c) streams in under GEMM1(c), W1(c+1) under GEMM2(c).  (The bf16 form -- one workgroup
 // per CU, an eighth of the matrix time per chunk -- stages W1 | W2 (| the chunk's h_pre rows, MODE 1) in a three-stage ring filled two
@@ -32,10 +32,6 @@
 #include "../../include/relpose_hip.h"
 
 namespace {
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-RP_DEV f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-RP_DEV f32x4v mfma16bf(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 constexpr int C = 192, HID = 768, CH = 32, NCHUNK = HID / CH;
 constexpr int W1T = CH * C, W2T = C * CH;                      // floats per staged tile (6144 each = 24 KB)
@@ -679,13 +675,7 @@ struct Variant {
   static constexpr int ROWS = NW * 16;
   static int grid(int tiles) {
     static int slots = 0;
-    if (!slots) {
-      int dev = 0, cus = 256, per_cu = 1;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mlp_fused_kernel<NW, WPS, MODE, BF, TRAIN>, NW * 64, 0);
-      slots = cus * (per_cu > 0 ? per_cu : 1);
-    }
+    if (!slots) slots = resident_slots<mlp_fused_kernel<NW, WPS, MODE, BF, TRAIN>, NW * 64>();
     const long long items = (long long)tiles * NCHUNK;
     return (int)(items < slots ? items : slots);
   }

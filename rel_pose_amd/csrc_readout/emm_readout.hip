@@ -13,14 +13,12 @@
 // Per score that leaves: v_exp, compare + two selects (running maximum and its index), one add and two fmas.
 // The dense A is a visualisation path: swap = 0 stores 16-byte runs straight from the accumulators (registers 4g .. 4g+3 of a lane
 // are four consecutive j of its row i), swap = 1 stores each register as a 128-byte run per half-wave (32 consecutive j of one row i).
-#include "../csrc/common.h"
+#include "../csrc/tile32.h"
 #include "../../include/relpose_readout.h"
 
 namespace {
 
-constexpr int NTOK = 576;
-constexpr int NTILE = NTOK / 32;
-constexpr int KST = 68;      // staged row: 64 features | -lse (log2 units) | 0 | n % 24 | n / 24
+// the 4 spare floats of a staged row (KST = 68): 64 features | -lse (log2 units) | 0 | n % 24 | n / 24
 constexpr int NW = 3;        // waves per workgroup: 96 owner tokens
 constexpr int NT = NW * 64;
 constexpr int GRID = 24;     // tokens per row of the 24 x 24 token grid
@@ -35,20 +33,6 @@ struct ReadoutP {
   int H, ZH, swap;
 };
 
-RP_DEV void tile_gload(const float* base, int ld, int tid, float4 (&r)[3]) {
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int f = min(tid + NT * j, 511);     // surplus threads duplicate the last element (no exec-masked guard)
-    r[j] = ld4(base + (long long)(f >> 4) * ld + (f & 15) * 4);
-  }
-}
-RP_DEV void tile_sstore(float* s, int tid, const float4 (&r)[3]) {
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int f = min(tid + NT * j, 511);
-    st4(s + (f >> 4) * KST + (f & 15) * 4, r[j]);
-  }
-}
 // the ride-along columns of loop token n = 32 t + tid (threads 0..31)
 RP_DEV void aux_sstore(float* s, int tid, int t, float nlse) {
   const int n = 32 * t + tid;
@@ -68,7 +52,7 @@ __global__ __launch_bounds__(NT, 3) void emm_readout_kernel(ReadoutP p) {
   const float* lb = p.loop + (long long)loop_img * NTOK * p.ld_loop + h * 64;
 
   float oreg[32];
-  {
+  {      // = load_owner (tile32.h), written out: the call reschedules this kernel's prologue, and this file's device code is kept as it was
     const float* orow = p.own + ((long long)own_img * NTOK + o0 + l31) * p.ld_own + h * 64 + 32 * hi;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -79,12 +63,13 @@ __global__ __launch_bounds__(NT, 3) void emm_readout_kernel(ReadoutP p) {
   // the 33rd MFMA step: k = 0 (lower half-wave) pairs 1 with -lse_owner, k = 1 (upper) pairs -lse_loop with 1
   const float bx = hi ? 1.0f : p.own_lse[zh * NTOK + o0 + l31] * p.own_mul;
 
+  const bf16x8 nopk[4] = {};      // (score_tile's bf16 operands: unused in its fp32 form)
   float4 kpre[3];
   // branch-free (every thread loads, threads 0..31 store): see emm_apply_kernel
   const float* lsrc = p.loop_lse + zh * NTOK + (tid & 31);
   float cpre = lsrc[0] * p.loop_mul;
-  tile_gload(lb, p.ld_loop, tid, kpre);
-  tile_sstore(Ks, tid, kpre);
+  tile_gload<NT>(lb, p.ld_loop, tid, kpre);
+  tile_sstore<NT, KST>(Ks, tid, kpre);
   aux_sstore(Ks, tid, 0, cpre);
   __syncthreads();
 
@@ -93,20 +78,11 @@ __global__ __launch_bounds__(NT, 3) void emm_readout_kernel(ReadoutP p) {
   for (int t = 0; t < NTILE; ++t) {
     const int cur = t & 1;
     if (t + 1 < NTILE) {
-      tile_gload(lb + (long long)(t + 1) * 32 * p.ld_loop, p.ld_loop, tid, kpre);
+      tile_gload<NT>(lb + (long long)(t + 1) * 32 * p.ld_loop, p.ld_loop, tid, kpre);
       cpre = lsrc[(t + 1) * 32] * p.loop_mul;
     }
     const float* K = Ks + cur * 32 * KST;
-    f32x16 s = zero16();      // S^T[loop][owner] in log2 units, then the exponent
-    const float* kr = K + l31 * KST + 32 * hi;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float4 kf = ld4(kr + 4 * c);
-      s = mfma32(kf.x, oreg[4 * c + 0], s);
-      s = mfma32(kf.y, oreg[4 * c + 1], s);
-      s = mfma32(kf.z, oreg[4 * c + 2], s);
-      s = mfma32(kf.w, oreg[4 * c + 3], s);
-    }
+    f32x16 s = score_tile<false>(K, l31, hi, oreg, nopk);      // S^T[loop][owner] in log2 units, then the exponent
     s = mfma32(hi ? K[l31 * KST + 64] : 1.0f, bx, s);
     const int n0 = 32 * t + 4 * hi;
 #pragma unroll
@@ -135,7 +111,7 @@ __global__ __launch_bounds__(NT, 3) void emm_readout_kernel(ReadoutP p) {
       }
     }
     if (t + 1 < NTILE) {
-      tile_sstore(Ks + (cur ^ 1) * 32 * KST, tid, kpre);
+      tile_sstore<NT, KST>(Ks + (cur ^ 1) * 32 * KST, tid, kpre);
       aux_sstore(Ks + (cur ^ 1) * 32 * KST, tid, t + 1, cpre);
     }
     __syncthreads();

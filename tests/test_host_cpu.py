@@ -493,6 +493,24 @@ def test_branch_free_gelu_constants_are_accurate():
     assert np.abs(grad - (phi + xd * np.exp(-0.5 * xd * xd) / np.sqrt(2 * np.pi))).max() < 5e-7
 
 
+def test_shared_device_primitives_have_one_definition():
+    """The hazard-sensitive device primitives (the LDS-DMA statement with its m0 save / restore, the hand-placed LDS reads, the 16x16
+    MFMA wrappers, the transpose read, the resident-slots query, the fp32 tile helpers) exist ONCE under csrc/ and csrc_readout/: a
+    kernel file that brings its own copy -- or names the instruction in a comment instead of the shared helper -- fails here."""
+    texts = {}
+    for d in ("csrc", "csrc_readout"):
+        for name in sorted(os.listdir(os.path.join(ROOT, "rel_pose_amd", d))):
+            path = os.path.join(ROOT, "rel_pose_amd", d, name)
+            if os.path.isfile(path) and name.endswith((".hip", ".h")):
+                texts[d + "/" + name] = open(path).read()
+    assert len(texts) >= 30
+    for needle in ("global_load_lds_dwordx4", "ds_read_b32 %0, %1 offset", "ds_read_b64_tr_b16", "__builtin_amdgcn_mfma_f32_16x16x4f32",
+                   "__builtin_amdgcn_mfma_f32_16x16x32_bf16", "__builtin_amdgcn_ds_read_tr16_b64_v4i16",
+                   "hipDeviceAttributeMultiprocessorCount", "RP_DEV f32x16 score_tile(", "void load_owner("):
+        holders = [f for f, t in texts.items() if needle in t]
+        assert len(holders) == 1, (needle, holders)
+
+
 def test_bf16_weight_copies_of_the_bf16_configuration():
     """Host side of the bf16 configuration's row-resident / fused-MLP kernels: ops.bf16_weight keeps a round-to-nearest-even bf16 copy of a
     weight until the weight is modified; ops._chunk_permuted_bf16 additionally stores the 768 hidden units of every 32-chunk in the order
