@@ -96,6 +96,8 @@ def main(argv=None):
     ap.add_argument("--transformer_depth", type=int, default=6)
     ap.add_argument("--matches", metavar="OUT.npz", default="",
                     help="also write the token correspondences the Essential Matrix Module formed (rel_pose_amd/readout.py)")
+    ap.add_argument("--eight_point", action="store_true",
+                    help="also print the classical pose of the Essential Matrix Module's matches (rel_pose_amd/eightpoint.py)")
     args = ap.parse_args(argv)
     args.fusion_transformer = True
     args.noess = "1" if args.noess else ""
@@ -124,7 +126,32 @@ def main(argv=None):
         print(preds[3:])
     if args.matches:
         write_matches(model, images, args.matches)
+    if args.eight_point:
+        print_eight_point(model, images, intr, png_size(args.img1), preds)
     return preds
+
+
+def png_size(path):
+    """(height, width) from the IHDR chunk"""
+    with open(path, "rb") as f:
+        head = f.read(24)
+    w, h = struct.unpack(">II", head[16:24])
+    return h, w
+
+
+def print_eight_point(model, images, intr, orig_hw, regressed):
+    """--eight_point: one line -- the pose (t unit, q xyzw) the weighted eight-point algorithm finds from the EMM's matches, the angle
+    between its rotation and the regressed one, and the angle between the two translation directions, in degrees.  `regressed` is the
+    [7] pose this script prints (t, q xyzw); the intrinsics follow the images' resize."""
+    H, W = images.shape[-2:]
+    sy, sx = H / orig_hw[0], W / orig_hw[1]
+    K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
+    mp = model.pose_from_matches(images, K)
+    p, r = mp.pose[0].double().cpu(), torch.from_numpy(np.asarray(regressed, dtype=np.float64))
+    dq = min(1.0, abs(float((p[3:] * r[3:]).sum()) / max(float(r[3:].norm()), 1e-30)))
+    dt = max(-1.0, min(1.0, float((p[:3] * r[:3]).sum()) / max(float(r[:3].norm()), 1e-30)))
+    print("eight-point pose x,y,z,qx,qy,qz,qw: %s ; rotation differs by %.3f deg, translation direction by %.3f deg"
+          % (" ".join("%.5f" % v for v in p.tolist()), 2 * np.degrees(np.arccos(dq)), np.degrees(np.arccos(dt))))
 
 
 def write_matches(model, images, path):

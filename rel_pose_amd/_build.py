@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so and librelpose_readout.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so and librelpose_eightpoint.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -12,6 +12,10 @@ SOURCES = ["gemm.hip", "gemm_dma.hip", "rowwise.hip", "attention.hip", "attentio
 READOUT_CSRC = os.path.join(HERE, "csrc_readout")
 READOUT_LIB = os.path.join(HERE, "librelpose_readout.so")
 READOUT_SOURCES = ["emm_readout.hip"]
+# the eight-point library (include/relpose_eightpoint.h): the same pattern, a third library with sources of its own
+EIGHTPOINT_CSRC = os.path.join(HERE, "csrc_eightpoint")
+EIGHTPOINT_LIB = os.path.join(HERE, "librelpose_eightpoint.so")
+EIGHTPOINT_SOURCES = ["eight_point.hip"]
 ARCH = "gfx950"
 
 
@@ -37,10 +41,14 @@ def readout_needs_build():
     return _stale(READOUT_LIB, READOUT_CSRC, READOUT_SOURCES, _readout_headers())
 
 
+def eightpoint_needs_build():
+    return _stale(EIGHTPOINT_LIB, EIGHTPOINT_CSRC, EIGHTPOINT_SOURCES, _eightpoint_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    Both libraries are built under the one lock, each only if it is stale (force: both, every translation unit)."""
+    All three libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -49,6 +57,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, LIB, CSRC, SOURCES, _headers())
             if force or readout_needs_build():
                 _build_locked(verbose, force, READOUT_LIB, READOUT_CSRC, READOUT_SOURCES, _readout_headers())
+            if force or eightpoint_needs_build():
+                _build_locked(verbose, force, EIGHTPOINT_LIB, EIGHTPOINT_CSRC, EIGHTPOINT_SOURCES, _eightpoint_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -61,6 +71,10 @@ def _headers():
 
 def _readout_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_readout.h")]
+
+
+def _eightpoint_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_eightpoint.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

@@ -113,6 +113,16 @@ READOUT_ABI_VERSION = _READOUT_CONSTS["RP_READOUT_ABI_VERSION"]
 READOUT_EXPORTS = tuple(_READOUT_PROTOTYPES)
 
 
+# the eight-point library (include/relpose_eightpoint.h -> librelpose_eightpoint.so): again the same parser, errcheck and RP_E* codes
+_EIGHTPOINT_LIB = None
+EIGHTPOINT_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_eightpoint.h")
+with open(EIGHTPOINT_HEADER) as _f:
+    _EIGHTPOINT_CONSTS, _, _EIGHTPOINT_PROTOTYPES, _EIGHTPOINT_STATUS = _header_contract(_f.read(), "relpose_eightpoint.h")
+EIGHTPOINT_ABI_VERSION = _EIGHTPOINT_CONSTS["RP_EIGHTPOINT_ABI_VERSION"]
+EIGHTPOINT_MAX_P, EIGHTPOINT_MAX_ITERS = _EIGHTPOINT_CONSTS["RP_EIGHTPOINT_MAX_P"], _EIGHTPOINT_CONSTS["RP_EIGHTPOINT_MAX_ITERS"]
+EIGHTPOINT_EXPORTS = tuple(_EIGHTPOINT_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -172,6 +182,32 @@ def load_readout():
         if name in _READOUT_STATUS:
             fn.errcheck = _raise_on_status
     _READOUT_LIB = lib
+    return lib
+
+
+def load_eightpoint():
+    """Load (building if absent or stale) and type librelpose_eightpoint.so.  Raises on any failure: there is no fallback."""
+    global _EIGHTPOINT_LIB
+    if _EIGHTPOINT_LIB is not None:
+        return _EIGHTPOINT_LIB
+    path = _build.EIGHTPOINT_LIB
+    if _build.eightpoint_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_eightpoint_abi_version.restype = c_int
+    if lib.rp_eightpoint_abi_version() != EIGHTPOINT_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_eightpoint_abi_version(), EIGHTPOINT_ABI_VERSION))
+    for name, (res, args) in _EIGHTPOINT_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _EIGHTPOINT_STATUS:
+            fn.errcheck = _raise_on_status
+    _EIGHTPOINT_LIB = lib
     return lib
 
 

@@ -153,6 +153,14 @@ class ViTEss(nn.Module):
         from . import readout
         return readout.correspondences(self, images, dense)
 
+    def pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None):
+        """images [B,2,3,H,W], intrinsics [B,2,4] = (fx, fy, cx, cy) in pixels of (H, W) -> eightpoint.MatchPose: the CLASSICAL pose of
+        the matches the Essential Matrix Module formed -- correspondences -> weighted eight-point with `iters` rounds of robust
+        re-weighting (tau: its scale; None = half a token pitch) -> E -> (R, t) by the cheirality vote.  eval() mode only; changes no
+        module state and does not write to `intrinsics`."""
+        from . import eightpoint
+        return eightpoint.pose_from_matches(self, images, intrinsics, heads, iters, tau)
+
     def forward(self, images, Gs, intrinsics=None, inference=False):
         if not hasattr(Gs, "data") or isinstance(Gs, np.ndarray):
             Gs = SE3(torch.from_numpy(np.asarray(Gs)).unsqueeze(0).to(images.device).float())

@@ -1,0 +1,222 @@
+"""The eight-point solver (include/relpose_eightpoint.h, librelpose_eightpoint.so, rel_pose_amd/eightpoint.py) as far as it goes without a
+GPU: the header and the binding derived from it, the build, the argument checks that precede any launch, the one-definition rule for
+the shared device code, the fp64 reference of tests/_eightpoint_ref.py against the truth, and the plain-torch assembly of matches."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from tests import _eightpoint_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_eightpoint_header_parses_and_the_library_exports_it():
+    from ctypes import c_int, c_void_p
+    from rel_pose_amd import _build, _lib
+    text = open(os.path.join(ROOT, "include", "relpose_eightpoint.h")).read()
+    consts, structs, sigs, status = _lib._header_contract(text, "relpose_eightpoint.h")
+    assert consts == {"RP_EIGHTPOINT_ABI_VERSION": 1, "RP_EIGHTPOINT_MAX_P": 1728, "RP_EIGHTPOINT_MAX_ITERS": 16} and not structs
+    assert (_lib.EIGHTPOINT_ABI_VERSION, _lib.EIGHTPOINT_MAX_P, _lib.EIGHTPOINT_MAX_ITERS) == (1, 1728, 16)
+    P, I = c_void_p, c_int
+    assert list(sigs.items()) == [("rp_eightpoint_abi_version", (c_int, [])),
+                                  ("rp_eight_point", (c_int, [P, P, P, P, P, P, P, I, I, I, P]))]
+    assert status == {"rp_eight_point"} and tuple(sigs) == _lib.EIGHTPOINT_EXPORTS
+    # the declarations as a C reader sees them (comments stripped), independently of the parser
+    declared = set(re.findall(r"\b(rp_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
+    assert declared == set(sigs)
+    typed = _lib.load_eightpoint()
+    raw = ctypes.CDLL(_build.EIGHTPOINT_LIB)
+    for sym in declared:
+        assert hasattr(raw, sym), "missing export: " + sym
+    assert typed.rp_eightpoint_abi_version() == _lib.EIGHTPOINT_ABI_VERSION
+    # a third library, not a change of the other two: it exports none of their names and their headers declare none of its
+    others = set(_lib.EXPORTS) | set(_lib.READOUT_EXPORTS)
+    assert not declared & others
+    for sym in others:
+        assert not hasattr(raw, sym), "librelpose_eightpoint.so exports " + sym
+    for h in ("relpose_hip.h", "relpose_readout.h"):
+        t = open(os.path.join(ROOT, "include", h)).read()
+        assert "rp_eight_point" not in t and "rp_eightpoint" not in t
+
+
+def test_launching_entry_point_checks_its_status():
+    from rel_pose_amd import _lib
+    lib = _lib.load_eightpoint()
+    hooked = {n for n in _lib.EIGHTPOINT_EXPORTS if getattr(lib, n).errcheck is not None}
+    assert hooked == {"rp_eight_point"}
+    assert lib.rp_eight_point.errcheck is _lib.load().rp_gemm.errcheck is _lib.load_readout().rp_emm_matches.errcheck
+    assert lib.rp_eightpoint_abi_version.restype is ctypes.c_int
+
+
+def test_eightpoint_build_is_a_library_of_its_own():
+    from rel_pose_amd import _build
+    assert os.path.basename(_build.EIGHTPOINT_LIB) == "librelpose_eightpoint.so"
+    assert len({_build.EIGHTPOINT_LIB, _build.READOUT_LIB, _build.LIB}) == 3
+    assert os.path.basename(_build.EIGHTPOINT_CSRC) == "csrc_eightpoint" and _build.EIGHTPOINT_SOURCES
+    assert not set(_build.EIGHTPOINT_SOURCES) & (set(_build.SOURCES) | set(_build.READOUT_SOURCES))
+    for s in _build.EIGHTPOINT_SOURCES:
+        assert os.path.isfile(os.path.join(ROOT, "rel_pose_amd", "csrc_eightpoint", s))
+        assert not os.path.exists(os.path.join(_build.CSRC, s)) and not os.path.exists(os.path.join(_build.READOUT_CSRC, s))
+    assert not _build.eightpoint_needs_build() or _build.build(verbose=False) == _build.LIB
+    assert not _build.eightpoint_needs_build() and not _build.readout_needs_build() and not _build.needs_build()
+
+
+def test_argument_checks_come_before_any_launch():
+    """no device is needed (or touched): the pointers are never dereferenced, the refusals precede the launch"""
+    from rel_pose_amd import _lib
+    lib = _lib.load_eightpoint()
+    P = ctypes.c_void_p
+    ok = [P(4096), P(8192), P(12288), P(16384), P(20480), P(24576), P(28672)]      # x1 x2 w tau E stat w_out
+
+    def call(ptrs=ok, P_=64, iters=2, n=3):
+        return lib.rp_eight_point(*ptrs, P_, iters, n, None)
+
+    def swap(i, v):
+        return ok[:i] + [v] + ok[i + 1:]
+    shape = r"rel_pose_amd: rp_eight_point failed: bad shape \(RP error -1\)"
+    unsupported = r"rel_pose_amd: rp_eight_point failed: unsupported \(RP error -4\)"
+    align = r"rel_pose_amd: rp_eight_point failed: misaligned pointer/stride \(RP error -2\)"
+    for kw in (dict(n=0), dict(n=-1), dict(P_=7), dict(P_=0), dict(iters=-1), dict(ptrs=swap(0, None)), dict(ptrs=swap(1, None)),
+               dict(ptrs=swap(4, None)), dict(ptrs=swap(5, None)), dict(ptrs=swap(3, None)), dict(ptrs=swap(3, None), iters=1)):
+        with pytest.raises(RuntimeError, match=shape):
+            call(**kw)
+    for kw in (dict(P_=1729), dict(P_=1 << 20), dict(iters=17)):
+        with pytest.raises(RuntimeError, match=unsupported):
+            call(**kw)
+    for kw in (dict(ptrs=swap(0, P(4100))), dict(ptrs=swap(1, P(8196))), dict(ptrs=swap(2, P(12290))), dict(ptrs=swap(3, P(16385))),
+               dict(ptrs=swap(4, P(20482))), dict(ptrs=swap(5, P(24579))), dict(ptrs=swap(6, P(28673)))):
+        with pytest.raises(RuntimeError, match=align):
+            call(**kw)
+
+
+def test_the_new_directory_brings_no_copy_of_a_shared_device_primitive():
+    """csrc_eightpoint/ includes csrc/common.h and csrc/svd3x3.h: none of the needles of test_shared_device_primitives_have_one_definition
+    occurs in it, and svd3x3_dev / rot are defined once across the three source directories"""
+    texts = {}
+    for d in ("csrc", "csrc_readout", "csrc_eightpoint"):
+        for name in sorted(os.listdir(os.path.join(ROOT, "rel_pose_amd", d))):
+            if name.endswith((".hip", ".h")):
+                texts[d + "/" + name] = open(os.path.join(ROOT, "rel_pose_amd", d, name)).read()
+    mine = {f: t for f, t in texts.items() if f.startswith("csrc_eightpoint/")}
+    assert set(mine) == {"csrc_eightpoint/eight_point.hip"}
+    for needle in ("global_load_lds_dwordx4", "ds_read_b32 %0, %1 offset", "ds_read_b64_tr_b16", "__builtin_amdgcn_mfma_f32_16x16x4f32",
+                   "__builtin_amdgcn_mfma_f32_16x16x32_bf16", "__builtin_amdgcn_ds_read_tr16_b64_v4i16",
+                   "hipDeviceAttributeMultiprocessorCount", "RP_DEV f32x16 score_tile(", "void load_owner("):
+        assert not [f for f, t in mine.items() if needle in t], needle
+    for definition in ("void svd3x3_dev(", "RP_DEV void rot("):
+        assert [f for f, t in texts.items() if definition in t] == ["csrc/svd3x3.h"], definition
+    text = mine["csrc_eightpoint/eight_point.hip"]
+    assert '#include "../csrc/common.h"' in text and '#include "../csrc/svd3x3.h"' in text
+    assert '#include "svd3x3.h"' in texts["csrc/geom.hip"]
+
+
+@pytest.mark.parametrize("P", [8, 9, 64, 1728])
+def test_reference_recovers_the_true_essential_matrix(P):
+    """exact fp64 correspondences: the reference returns E_true (singular values 1, 1, 0) up to sign; measured 2e-15 .. 4e-14"""
+    x1, x2, Et = R.scenes(3, P, seed=1)
+    E, stat, w = R.eight_point_ref(x1, x2)
+    assert float(R.up_to_sign(E, Et).max()) < 2e-13
+    assert np.allclose(np.linalg.svd(E, compute_uv=False), [1, 1, 0], atol=1e-13)
+    assert float(stat[:, 0].max()) < 1e-13 and float(stat[:, 1].min()) > 1e-3      # one null direction, and only one
+    assert np.allclose(stat[:, 2], 1, atol=1e-11) and np.array_equal(stat[:, 3], np.full(3, float(P))) and np.array_equal(w, np.ones((3, P)))
+    # the sign rule
+    flat = E.reshape(3, 9)
+    assert bool((flat[np.arange(3), np.abs(flat).argmax(-1)] > 0).all())
+    # the points satisfy the epipolar constraint of the convention
+    assert float(R.sampson64(E, x1, x2).max()) < 1e-24
+
+
+def test_reference_weights_reweighting_and_degenerate_problems():
+    x1, x2, Et = R.scenes(2, 40, seed=2)
+    rng = np.random.default_rng(0)
+    x2o = x2.copy()
+    x2o[:, :6] = rng.uniform(-0.5, 0.5, (2, 6, 2))                       # six gross outliers ...
+    w = np.ones((2, 40))
+    w[:, :6] = 0                                                         # ... with weight 0 (and -1: counts as 0) do not matter
+    assert float(R.up_to_sign(R.eight_point_ref(x1, x2o, w)[0], Et).max()) < 2e-13
+    assert float(R.up_to_sign(R.eight_point_ref(x1, x2o, np.where(w > 0, w, -1.0))[0], Et).max()) < 2e-13
+    assert float(R.up_to_sign(R.eight_point_ref(x1, x2o)[0], Et).min()) > 1e-3
+    # one round of re-weighting is the solve with the Cauchy weights of the first result
+    tau = np.array([0.02, 0.05])
+    E0, _, w0 = R.eight_point_ref(x1, x2o)
+    E1, s1, w1 = R.eight_point_ref(x1, x2o, None, tau, 1)
+    assert np.array_equal(w1, 1 / (1 + R.sampson64(E0, x1, x2o) / tau[:, None] ** 2))
+    assert np.array_equal(E1, R.eight_point_ref(x1, x2o, w1)[0]) and np.isclose(s1[:, 3], w1.sum(-1)).all()
+    # degenerate: seven positive weights; all points coincident in image 2
+    w7 = np.zeros((2, 40))
+    w7[:, 3:10] = 0.5
+    E, stat, wo = R.eight_point_ref(x1, x2, w7, tau, 2)
+    assert not E.any() and np.array_equal(stat, [[0, 0, 0, 3.5]] * 2) and np.array_equal(wo, w7)
+    E, stat, wo = R.eight_point_ref(x1, np.broadcast_to(x2[:, :1], x2.shape).copy())
+    assert not E.any() and np.array_equal(stat, [[0, 0, 0, 40.0]] * 2)
+
+
+def test_float32_restatement_is_within_the_perturbation_bound():
+    """the calibration of the GPU tests' bound: |E_f32 - E_ref| <= C/8 eps32 sigma_1 / sigma_8 with the C of tests/test_gpu_eightpoint.py
+    on a subset of its inputs (the whole set is measured in that module's docstring)"""
+    from tests.test_gpu_eightpoint import C_PARITY, parity_inputs
+    for P, n in ((8, 130), (9, 3), (257, 1)):
+        for weighted in (False, True):
+            x1, x2, w = parity_inputs(P, n, weighted)
+            Er, sr, _ = R.eight_point_ref(x1, x2, w)
+            Ef, sf, _ = R.eight_point_f32(x1, x2, w)
+            ratio = R.up_to_sign(Ef, Er) / (R.EPS32 / sr[:, 1])
+            assert float(ratio.max()) <= C_PARITY / 8, (P, weighted, float(ratio.max()))
+
+
+def _hand_made(B=2, H=2):
+    """B pairs, H heads: every image's rows follow a permutation of their own; in image 1 of pair 0, head 1, rows 5 and 7 both pick
+    the column row 7 owns, so row 5 is not mutual"""
+    from rel_pose_amd import readout
+    g = torch.Generator().manual_seed(11)
+    perms = torch.stack([torch.stack([torch.randperm(576, generator=g) for _ in range(H)]) for _ in range(2 * B)])
+    row = perms.clone().int()
+    col = torch.argsort(perms, -1).int()
+    row[1, 1, 5] = row[1, 1, 7]
+    stat = torch.rand(2 * B, H, 576, 4, generator=g) + 0.1
+    return readout.Correspondences(row, stat, col, stat.clone(), readout.mutual(row, col), None), perms
+
+
+def test_assemble_matches_on_hand_made_correspondences():
+    from rel_pose_amd import eightpoint, readout
+    corr, perms = _hand_made()
+    intr = torch.tensor([[[400.0, 410.0, 250.0, 190.0], [380.0, 390.0, 260.0, 200.0]],
+                         [[500.0, 505.0, 256.0, 192.0], [300.0, 310.0, 240.0, 180.0]]])
+    keep = intr.clone()
+    hw = (384, 512)
+    x1, x2, w = eightpoint.assemble_matches(corr, intr, hw, heads=(0, 1))
+    assert torch.equal(intr, keep)                                        # only read
+    assert x1.shape == (2, 1152, 2) and x2.shape == (2, 1152, 2) and w.shape == (2, 1152)
+    assert x1.is_contiguous() and x2.is_contiguous() and w.is_contiguous() and x1.dtype == torch.float32
+    c = readout.token_centres(hw)
+    for b in range(2):
+        z = 2 * b + 1
+        for j, h in enumerate((0, 1)):
+            s = slice(576 * j, 576 * (j + 1))
+            assert torch.equal(x1[b, s], readout.normalised(c, intr[b, 0]))
+            assert torch.equal(x2[b, s], readout.normalised(c[corr.row_idx[z, h].long()], intr[b, 1]))
+            assert torch.equal(w[b, s], corr.row_stat[z, h, :, 0] * corr.mutual[z, h])
+    # the one non-mutual row has weight 0, every other its confidence (> 0)
+    assert float(w[0, 576 + 5]) == 0 and int((w == 0).sum()) == 1 and not bool(corr.mutual[1, 1, 5])
+    # a subset and another order of heads
+    y1, y2, v = eightpoint.assemble_matches(corr, intr, hw, heads=(1,))
+    assert y1.shape == (2, 576, 2) and torch.equal(y2, x2[:, 576:]) and torch.equal(v, w[:, 576:])
+    with pytest.raises(ValueError, match="intrinsics"):
+        eightpoint.assemble_matches(corr, intr[:1], hw)
+    tau = eightpoint.default_tau(intr, hw)
+    assert tau.shape == (2,) and torch.allclose(tau, torch.tensor([0.5 * (512 / 24) / 400.0, 0.5 * (512 / 24) / 500.0]))
+
+
+def test_pose_from_matches_refuses_what_it_cannot_read_before_touching_a_device():
+    from rel_pose_amd.model import ViTEss
+    from tests.test_host_cpu import make_args
+    intr = torch.ones(1, 2, 4)
+    m = ViTEss(make_args())
+    assert m.training
+    with pytest.raises(RuntimeError, match="eval"):
+        m.pose_from_matches(torch.zeros(1, 2, 3, 64, 64), intr)
+    assert torch.equal(intr, torch.ones(1, 2, 4))
