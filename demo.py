@@ -98,7 +98,14 @@ def main(argv=None):
                     help="also write the token correspondences the Essential Matrix Module formed (rel_pose_amd/readout.py)")
     ap.add_argument("--eight_point", action="store_true",
                     help="also print the classical pose of the Essential Matrix Module's matches (rel_pose_amd/eightpoint.py)")
+    ap.add_argument("--refine", type=int, default=0, metavar="N",
+                    help="with --eight_point: also print that pose after N refinement iterations on the robust Sampson cost "
+                         "(rel_pose_amd/refine.py) and the cost of the regressed, the eight-point and the refined pose")
     args = ap.parse_args(argv)
+    if args.refine and not args.eight_point:
+        ap.error("--refine needs --eight_point")
+    if args.refine < 0:
+        ap.error("--refine takes a positive number of iterations")
     args.fusion_transformer = True
     args.noess = "1" if args.noess else ""
     print("predicting pose on %s and %s using model %s" % (args.img1, args.img2, args.ckpt or "<random init>"))
@@ -127,7 +134,7 @@ def main(argv=None):
     if args.matches:
         write_matches(model, images, args.matches)
     if args.eight_point:
-        print_eight_point(model, images, intr, png_size(args.img1), preds)
+        print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine)
     return preds
 
 
@@ -139,19 +146,39 @@ def png_size(path):
     return h, w
 
 
-def print_eight_point(model, images, intr, orig_hw, regressed):
+def _angles_line(name, p, r):
+    dq = min(1.0, abs(float((p[3:] * r[3:]).sum()) / max(float(r[3:].norm()), 1e-30)))
+    dt = max(-1.0, min(1.0, float((p[:3] * r[:3]).sum()) / max(float(r[:3].norm()), 1e-30)))
+    print("%s pose x,y,z,qx,qy,qz,qw: %s ; rotation differs by %.3f deg, translation direction by %.3f deg"
+          % (name, " ".join("%.5f" % v for v in p.tolist()), 2 * np.degrees(np.arccos(dq)), np.degrees(np.arccos(dt))))
+
+
+def print_eight_point(model, images, intr, orig_hw, regressed, refine=0):
     """--eight_point: one line -- the pose (t unit, q xyzw) the weighted eight-point algorithm finds from the EMM's matches, the angle
     between its rotation and the regressed one, and the angle between the two translation directions, in degrees.  `regressed` is the
-    [7] pose this script prints (t, q xyzw); the intrinsics follow the images' resize."""
+    [7] pose this script prints (t, q xyzw); the intrinsics follow the images' resize.  refine = N > 0 (--refine N): one more line of the same
+    form for the pose after N refinement iterations, and one with the mean robust Sampson cost of the three poses."""
     H, W = images.shape[-2:]
     sy, sx = H / orig_hw[0], W / orig_hw[1]
     K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
-    mp = model.pose_from_matches(images, K)
-    p, r = mp.pose[0].double().cpu(), torch.from_numpy(np.asarray(regressed, dtype=np.float64))
-    dq = min(1.0, abs(float((p[3:] * r[3:]).sum()) / max(float(r[3:].norm()), 1e-30)))
-    dt = max(-1.0, min(1.0, float((p[:3] * r[:3]).sum()) / max(float(r[:3].norm()), 1e-30)))
-    print("eight-point pose x,y,z,qx,qy,qz,qw: %s ; rotation differs by %.3f deg, translation direction by %.3f deg"
-          % (" ".join("%.5f" % v for v in p.tolist()), 2 * np.degrees(np.arccos(dq)), np.degrees(np.arccos(dt))))
+    r = torch.from_numpy(np.asarray(regressed, dtype=np.float64))
+    if not refine:
+        _angles_line("eight-point", model.pose_from_matches(images, K).pose[0].double().cpu(), r)
+        return
+    # --refine N: one more line of the same form for the refined pose, then the mean robust Sampson cost (the iters = 0 scorer of
+    # rel_pose_amd/refine.py) of the three poses against the same matches, base weights and tau
+    from rel_pose_amd import eightpoint
+    from rel_pose_amd import refine as refine_
+    hw = (int(H), int(W))
+    rp = model.refined_pose_from_matches(images, K, refine=refine)
+    _angles_line("eight-point", rp.initial.pose[0].double().cpu(), r)
+    _angles_line("refined", rp.pose[0].double().cpu(), r)
+    x1, x2, w = eightpoint.assemble_matches(model.correspondences(images), K, hw)
+    tau = eightpoint.default_tau(K, hw).contiguous()
+    poses = torch.cat([torch.from_numpy(np.asarray(regressed, dtype=np.float32))[None].cuda(), rp.initial.pose, rp.pose])
+    cost = refine_.refine_pose(poses, x1.expand(3, -1, -1).contiguous(), x2.expand(3, -1, -1).contiguous(), w.expand(3, -1).contiguous(),
+                               tau=tau.expand(3).contiguous(), iters=0).stat[:, 0].cpu().tolist()
+    print("mean robust Sampson cost of the matches: regressed %.6e, eight-point %.6e, refined %.6e" % tuple(cost))
 
 
 def write_matches(model, images, path):

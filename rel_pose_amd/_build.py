@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so and librelpose_eightpoint.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so and librelpose_refine.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -16,6 +16,10 @@ READOUT_SOURCES = ["emm_readout.hip"]
 EIGHTPOINT_CSRC = os.path.join(HERE, "csrc_eightpoint")
 EIGHTPOINT_LIB = os.path.join(HERE, "librelpose_eightpoint.so")
 EIGHTPOINT_SOURCES = ["eight_point.hip"]
+# the refinement library (include/relpose_refine.h): a fourth library, the same pattern again
+REFINE_CSRC = os.path.join(HERE, "csrc_refine")
+REFINE_LIB = os.path.join(HERE, "librelpose_refine.so")
+REFINE_SOURCES = ["refine_pose.hip"]
 ARCH = "gfx950"
 
 
@@ -45,10 +49,14 @@ def eightpoint_needs_build():
     return _stale(EIGHTPOINT_LIB, EIGHTPOINT_CSRC, EIGHTPOINT_SOURCES, _eightpoint_headers())
 
 
+def refine_needs_build():
+    return _stale(REFINE_LIB, REFINE_CSRC, REFINE_SOURCES, _refine_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All three libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All four libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -59,6 +67,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, READOUT_LIB, READOUT_CSRC, READOUT_SOURCES, _readout_headers())
             if force or eightpoint_needs_build():
                 _build_locked(verbose, force, EIGHTPOINT_LIB, EIGHTPOINT_CSRC, EIGHTPOINT_SOURCES, _eightpoint_headers())
+            if force or refine_needs_build():
+                _build_locked(verbose, force, REFINE_LIB, REFINE_CSRC, REFINE_SOURCES, _refine_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -75,6 +85,10 @@ def _readout_headers():
 
 def _eightpoint_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_eightpoint.h")]
+
+
+def _refine_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_refine.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

@@ -123,6 +123,16 @@ EIGHTPOINT_MAX_P, EIGHTPOINT_MAX_ITERS = _EIGHTPOINT_CONSTS["RP_EIGHTPOINT_MAX_P
 EIGHTPOINT_EXPORTS = tuple(_EIGHTPOINT_PROTOTYPES)
 
 
+# the refinement library (include/relpose_refine.h -> librelpose_refine.so): once more the same parser, errcheck and RP_E* codes
+_REFINE_LIB = None
+REFINE_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_refine.h")
+with open(REFINE_HEADER) as _f:
+    _REFINE_CONSTS, _, _REFINE_PROTOTYPES, _REFINE_STATUS = _header_contract(_f.read(), "relpose_refine.h")
+REFINE_ABI_VERSION = _REFINE_CONSTS["RP_REFINE_ABI_VERSION"]
+REFINE_MAX_P, REFINE_MAX_ITERS = _REFINE_CONSTS["RP_REFINE_MAX_P"], _REFINE_CONSTS["RP_REFINE_MAX_ITERS"]
+REFINE_EXPORTS = tuple(_REFINE_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -208,6 +218,32 @@ def load_eightpoint():
         if name in _EIGHTPOINT_STATUS:
             fn.errcheck = _raise_on_status
     _EIGHTPOINT_LIB = lib
+    return lib
+
+
+def load_refine():
+    """Load (building if absent or stale) and type librelpose_refine.so.  Raises on any failure: there is no fallback."""
+    global _REFINE_LIB
+    if _REFINE_LIB is not None:
+        return _REFINE_LIB
+    path = _build.REFINE_LIB
+    if _build.refine_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_refine_abi_version.restype = c_int
+    if lib.rp_refine_abi_version() != REFINE_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_refine_abi_version(), REFINE_ABI_VERSION))
+    for name, (res, args) in _REFINE_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _REFINE_STATUS:
+            fn.errcheck = _raise_on_status
+    _REFINE_LIB = lib
     return lib
 
 

@@ -15,17 +15,18 @@
 //   finish   column norms = singular values (one nine-value reduction); the column of V that belongs to the smallest is F^;
 //            F = T2^T F^ T1; svd3x3_dev; E = u0 v0^T + u1 v1^T; the sign rule.  Every thread computes this redundantly (it needs E for
 //            the next round's Sampson distances), thread 0 stores.
-// Reductions: within a wave by xor shuffles (wave_sum), across the four waves through LDS, summed by every thread in the same fixed
+// Reductions (csrc/block_sum.h): within a wave by xor shuffles, across the four waves through LDS, summed by every thread in the same fixed
 // order -- (alpha, beta, gamma) are bit-identical in all 256 threads, so the skip decision and (c, s) are uniform and every result is
 // bit-identical from call to call.  No atomics, no workspace; nothing is read from an output.
 #include "../csrc/common.h"
+#include "../csrc/block_sum.h"
 #include "../csrc/svd3x3.h"
 #include "../../include/relpose_eightpoint.h"
 
 namespace {
 
-constexpr int NT = 256;                              // threads per workgroup
-constexpr int NW = NT / 64;
+constexpr int NT = BLOCK_SUM_THREADS;                // threads per workgroup
+constexpr int NW = BLOCK_SUM_WAVES;
 constexpr int MAXP = RP_EIGHTPOINT_MAX_P;
 constexpr int ROWS = (MAXP + NT - 1) / NT;           // rows of a column one thread owns: 7
 constexpr int SWEEPS = 9;
@@ -37,24 +38,6 @@ struct Smem {
   float red[2][NW][RED];
   float V[9][9];               // V[column][row]
 };
-
-// sums of v[0..N-1] over the workgroup, in every thread.  One barrier per call: `phase` alternates between the two halves of the buffer,
-// and whoever writes a half again (two calls later) has passed the barrier of the call in between, which every thread reaches only
-// after its reads of this call.
-template <int N>
-RP_DEV void block_sum(float (&v)[N], Smem& sm, int& phase) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = wave_sum(v[i]);
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) sm.red[phase][wave][i] = v[i];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = ((sm.red[phase][0][i] + sm.red[phase][1][i]) + sm.red[phase][2][i]) + sm.red[phase][3][i];
-  phase ^= 1;
-}
 
 // Sampson distance of x1 <-> x2 under e (row-major), as rel_pose_amd/readout.py: sampson_distance; 0 where the denominator is 0
 RP_DEV float sampson(const float (&e)[9], float2 a, float2 b) {
@@ -98,7 +81,7 @@ __global__ __launch_bounds__(NT) void eight_point_kernel(const float* __restrict
       acc[4] += wt * (c.x - o2.x);
       acc[5] += wt * (c.y - o2.y);
     }
-    block_sum<6>(acc, sm, phase);
+    block_sum(acc, sm.red, phase);
     const float wsum = acc[0];
     bool degenerate = acc[1] < 8.f;                // (uniform: every thread holds the same sums)
     float c1x = 0.f, c1y = 0.f, c2x = 0.f, c2y = 0.f, s1 = 0.f, s2 = 0.f;
@@ -114,7 +97,7 @@ __global__ __launch_bounds__(NT) void eight_point_kernel(const float* __restrict
         m[0] += wt * sqrtf(ax * ax + ay * ay);
         m[1] += wt * sqrtf(bx * bx + by * by);
       }
-      block_sum<2>(m, sm, phase);
+      block_sum(m, sm.red, phase);
       const float m1 = m[0] / wsum, m2 = m[1] / wsum;
       degenerate = !(m1 >= MIN_SCALE) || !(m2 >= MIN_SCALE);
       if (!degenerate) {
@@ -160,7 +143,7 @@ __global__ __launch_bounds__(NT) void eight_point_kernel(const float* __restrict
             g[1] += yr[i] * yr[i];
             g[2] += xr[i] * yr[i];
           }
-          block_sum<3>(g, sm, phase);
+          block_sum(g, sm.red, phase);
           const float al = g[0], be = g[1], ga = g[2];
           if (fabsf(ga) > 1e-12f * sqrtf(al * be) && ga != 0.f) {
             const float zeta = (be - al) / (2.f * ga);
@@ -188,7 +171,7 @@ __global__ __launch_bounds__(NT) void eight_point_kernel(const float* __restrict
 #pragma unroll
       for (int j = 0; j < 9; ++j) sg2[j] += sm.col[j][r] * sm.col[j][r];
     }
-    block_sum<9>(sg2, sm, phase);                  // (its barrier also publishes V)
+    block_sum(sg2, sm.red, phase);                  // (its barrier also publishes V)
     int jmin = 0;
     float smax = sg2[0];
 #pragma unroll

@@ -161,6 +161,13 @@ class ViTEss(nn.Module):
         from . import eightpoint
         return eightpoint.pose_from_matches(self, images, intrinsics, heads, iters, tau)
 
+    def refined_pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None, refine=10):
+        """pose_from_matches followed by `refine` Levenberg-Marquardt iterations on the robust Sampson cost of the same matches (their base
+        weights, the same tau) over the five degrees of freedom of (R, t) -> refine.RefinedMatchPose; its `initial` is what
+        pose_from_matches returns.  eval() mode only; changes no module state and does not write to `intrinsics`."""
+        from . import refine as refine_
+        return refine_.refined_pose_from_matches(self, images, intrinsics, heads, iters, tau, refine)
+
     def forward(self, images, Gs, intrinsics=None, inference=False):
         if not hasattr(Gs, "data") or isinstance(Gs, np.ndarray):
             Gs = SE3(torch.from_numpy(np.asarray(Gs)).unsqueeze(0).to(images.device).float())

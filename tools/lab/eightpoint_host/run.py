@@ -30,6 +30,9 @@ def build():
     svd = open(os.path.join(pkg, "csrc", "svd3x3.h")).read().replace('#include "common.h"', '#include "shim.h"')
     k = open(os.path.join(pkg, "csrc_eightpoint", "eight_point.hip")).read()
     k = k.replace('#include "../csrc/common.h"', '#include "shim.h"').replace('#include "../csrc/svd3x3.h"', '#include "svd3x3.h"')
+    k = k.replace('#include "../csrc/block_sum.h"', '#include "block_sum.h"')
+    red = open(os.path.join(pkg, "csrc", "block_sum.h")).read().replace('#include "common.h"', '#include "shim.h"')
+    open(os.path.join(TMP, "block_sum.h"), "w").write(red)
     k = re.sub(r'#include "../../include/(\w+\.h)"', r'#include "\1"', k)
     open(os.path.join(TMP, "svd3x3.h"), "w").write(svd)
     open(os.path.join(TMP, "kernel.cpp"), "w").write(k)
