@@ -101,7 +101,15 @@ def main(argv=None):
     ap.add_argument("--refine", type=int, default=0, metavar="N",
                     help="with --eight_point: also print that pose after N refinement iterations on the robust Sampson cost "
                          "(rel_pose_amd/refine.py) and the cost of the regressed, the eight-point and the refined pose")
+    ap.add_argument("--consensus", type=int, default=0, metavar="M",
+                    help="with --eight_point: also print the pose of the chain started from the best of M seeded minimal eight-point "
+                         "hypotheses (rel_pose_amd/consensus.py); with --refine its cost joins the cost line")
+    ap.add_argument("--seed", type=int, default=0, help="with --consensus: the seed of its sampler")
     args = ap.parse_args(argv)
+    if args.consensus and not args.eight_point:
+        ap.error("--consensus needs --eight_point")
+    if args.consensus < 0:
+        ap.error("--consensus takes a positive number of hypotheses")
     if args.refine and not args.eight_point:
         ap.error("--refine needs --eight_point")
     if args.refine < 0:
@@ -134,7 +142,7 @@ def main(argv=None):
     if args.matches:
         write_matches(model, images, args.matches)
     if args.eight_point:
-        print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine)
+        print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine, args.consensus, args.seed)
     return preds
 
 
@@ -153,17 +161,22 @@ def _angles_line(name, p, r):
           % (name, " ".join("%.5f" % v for v in p.tolist()), 2 * np.degrees(np.arccos(dq)), np.degrees(np.arccos(dt))))
 
 
-def print_eight_point(model, images, intr, orig_hw, regressed, refine=0):
+def print_eight_point(model, images, intr, orig_hw, regressed, refine=0, consensus=0, seed=0):
     """--eight_point: one line -- the pose (t unit, q xyzw) the weighted eight-point algorithm finds from the EMM's matches, the angle
     between its rotation and the regressed one, and the angle between the two translation directions, in degrees.  `regressed` is the
     [7] pose this script prints (t, q xyzw); the intrinsics follow the images' resize.  refine = N > 0 (--refine N): one more line of the same
-    form for the pose after N refinement iterations, and one with the mean robust Sampson cost of the three poses."""
+    form for the pose after N refinement iterations, and one with the mean robust Sampson cost of the three poses.  consensus = M > 0
+    (--consensus M): one more pose line, the chain started from the best of M hypotheses (refined N times, too); its cost joins the
+    cost line."""
     H, W = images.shape[-2:]
     sy, sx = H / orig_hw[0], W / orig_hw[1]
     K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
     r = torch.from_numpy(np.asarray(regressed, dtype=np.float64))
+    cp = model.consensus_pose_from_matches(images, K, hypotheses=consensus, seed=seed, refine=refine) if consensus else None
     if not refine:
         _angles_line("eight-point", model.pose_from_matches(images, K).pose[0].double().cpu(), r)
+        if cp is not None:
+            _angles_line("consensus", cp.pose[0].double().cpu(), r)
         return
     # --refine N: one more line of the same form for the refined pose, then the mean robust Sampson cost (the iters = 0 scorer of
     # rel_pose_amd/refine.py) of the three poses against the same matches, base weights and tau
@@ -173,12 +186,15 @@ def print_eight_point(model, images, intr, orig_hw, regressed, refine=0):
     rp = model.refined_pose_from_matches(images, K, refine=refine)
     _angles_line("eight-point", rp.initial.pose[0].double().cpu(), r)
     _angles_line("refined", rp.pose[0].double().cpu(), r)
+    if cp is not None:
+        _angles_line("consensus", cp.pose[0].double().cpu(), r)
     x1, x2, w = eightpoint.assemble_matches(model.correspondences(images), K, hw)
     tau = eightpoint.default_tau(K, hw).contiguous()
     poses = torch.cat([torch.from_numpy(np.asarray(regressed, dtype=np.float32))[None].cuda(), rp.initial.pose, rp.pose])
     cost = refine_.refine_pose(poses, x1.expand(3, -1, -1).contiguous(), x2.expand(3, -1, -1).contiguous(), w.expand(3, -1).contiguous(),
                                tau=tau.expand(3).contiguous(), iters=0).stat[:, 0].cpu().tolist()
-    print("mean robust Sampson cost of the matches: regressed %.6e, eight-point %.6e, refined %.6e" % tuple(cost))
+    line = "mean robust Sampson cost of the matches: regressed %.6e, eight-point %.6e, refined %.6e" % tuple(cost)
+    print(line if cp is None else line + ", consensus %.6e" % float(cp.stat[0, 1]))
 
 
 def write_matches(model, images, path):

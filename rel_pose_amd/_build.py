@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so and librelpose_refine.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so and librelpose_consensus.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -20,6 +20,10 @@ EIGHTPOINT_SOURCES = ["eight_point.hip"]
 REFINE_CSRC = os.path.join(HERE, "csrc_refine")
 REFINE_LIB = os.path.join(HERE, "librelpose_refine.so")
 REFINE_SOURCES = ["refine_pose.hip"]
+# the consensus library (include/relpose_consensus.h): a fifth library, the same pattern once more
+CONSENSUS_CSRC = os.path.join(HERE, "csrc_consensus")
+CONSENSUS_LIB = os.path.join(HERE, "librelpose_consensus.so")
+CONSENSUS_SOURCES = ["consensus.hip"]
 ARCH = "gfx950"
 
 
@@ -53,10 +57,14 @@ def refine_needs_build():
     return _stale(REFINE_LIB, REFINE_CSRC, REFINE_SOURCES, _refine_headers())
 
 
+def consensus_needs_build():
+    return _stale(CONSENSUS_LIB, CONSENSUS_CSRC, CONSENSUS_SOURCES, _consensus_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All four libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All five libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -69,6 +77,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, EIGHTPOINT_LIB, EIGHTPOINT_CSRC, EIGHTPOINT_SOURCES, _eightpoint_headers())
             if force or refine_needs_build():
                 _build_locked(verbose, force, REFINE_LIB, REFINE_CSRC, REFINE_SOURCES, _refine_headers())
+            if force or consensus_needs_build():
+                _build_locked(verbose, force, CONSENSUS_LIB, CONSENSUS_CSRC, CONSENSUS_SOURCES, _consensus_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -89,6 +99,10 @@ def _eightpoint_headers():
 
 def _refine_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_refine.h")]
+
+
+def _consensus_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_consensus.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

@@ -133,6 +133,16 @@ REFINE_MAX_P, REFINE_MAX_ITERS = _REFINE_CONSTS["RP_REFINE_MAX_P"], _REFINE_CONS
 REFINE_EXPORTS = tuple(_REFINE_PROTOTYPES)
 
 
+# the consensus library (include/relpose_consensus.h -> librelpose_consensus.so): the same parser, errcheck and RP_E* codes a fifth time
+_CONSENSUS_LIB = None
+CONSENSUS_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_consensus.h")
+with open(CONSENSUS_HEADER) as _f:
+    _CONSENSUS_CONSTS, _, _CONSENSUS_PROTOTYPES, _CONSENSUS_STATUS = _header_contract(_f.read(), "relpose_consensus.h")
+CONSENSUS_ABI_VERSION = _CONSENSUS_CONSTS["RP_CONSENSUS_ABI_VERSION"]
+CONSENSUS_MAX_P, CONSENSUS_MAX_M = _CONSENSUS_CONSTS["RP_CONSENSUS_MAX_P"], _CONSENSUS_CONSTS["RP_CONSENSUS_MAX_M"]
+CONSENSUS_EXPORTS = tuple(_CONSENSUS_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -244,6 +254,32 @@ def load_refine():
         if name in _REFINE_STATUS:
             fn.errcheck = _raise_on_status
     _REFINE_LIB = lib
+    return lib
+
+
+def load_consensus():
+    """Load (building if absent or stale) and type librelpose_consensus.so.  Raises on any failure: there is no fallback."""
+    global _CONSENSUS_LIB
+    if _CONSENSUS_LIB is not None:
+        return _CONSENSUS_LIB
+    path = _build.CONSENSUS_LIB
+    if _build.consensus_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_consensus_abi_version.restype = c_int
+    if lib.rp_consensus_abi_version() != CONSENSUS_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_consensus_abi_version(), CONSENSUS_ABI_VERSION))
+    for name, (res, args) in _CONSENSUS_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _CONSENSUS_STATUS:
+            fn.errcheck = _raise_on_status
+    _CONSENSUS_LIB = lib
     return lib
 
 

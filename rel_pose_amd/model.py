@@ -168,6 +168,14 @@ class ViTEss(nn.Module):
         from . import refine as refine_
         return refine_.refined_pose_from_matches(self, images, intrinsics, heads, iters, tau, refine)
 
+    def consensus_pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), hypotheses=1024, seed=0, iters=4, tau=None, refine=10):
+        """refined_pose_from_matches started from a consensus instead of the all-data solve: `hypotheses` minimal eight-point samples drawn
+        from `seed`, each scored on all matches; the best one's Cauchy weights are the base weights of the eight-point solve that the
+        refinement (on the matches' own base weights) then starts from -> consensus.ConsensusMatchPose.  The same seed gives the same
+        bits.  eval() mode only; changes no module state and does not write to `intrinsics`."""
+        from . import consensus
+        return consensus.consensus_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, iters, tau, refine)
+
     def forward(self, images, Gs, intrinsics=None, inference=False):
         if not hasattr(Gs, "data") or isinstance(Gs, np.ndarray):
             Gs = SE3(torch.from_numpy(np.asarray(Gs)).unsqueeze(0).to(images.device).float())
