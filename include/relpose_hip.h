@@ -630,6 +630,8 @@ int rp_augment_pairs(const unsigned char* images, const float* params, float* ou
  *   rp_essential_from_pose: E[n][3][3] = [t]x R(q) from poses [n][7] = (t, q xyzw); q is normalised internally.
  *   rp_svd3x3: A[n][3][3] = U diag(S) V^T, S descending and non-negative, U and V orthogonal (U completed by cross
  *     products when A is rank deficient, as an essential matrix is).  One lane per matrix, one-sided Jacobi, registers only.
+ *     Domain: finite float32 entries whose largest magnitude is a normal number (A is scaled by an exact power of two inside, so
+ *     results do not depend on the scale of A; S overflows only where sigma_1 itself is not a float32).
  * ------------------------------------------------------------------------------------------- */
 int rp_essential_from_pose(const float* pose, float* E, int n, void* stream);
 int rp_svd3x3(const float* A, float* U, float* S, float* V, int n, void* stream);

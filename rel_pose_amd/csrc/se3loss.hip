@@ -12,6 +12,7 @@
 namespace {
 
 constexpr int ND = 14;
+constexpr float C_SERIES = 0.5f;   // se3.py: C_SERIES (see se3_log_norms)
 
 struct Dual {
   float v;
@@ -147,9 +148,15 @@ RP_DEV V3 so3_log(const Q4& q) {
 RP_DEV void se3_log_norms(const Pose& p, Dual& ntau, Dual& nphi) {
   const V3 phi = so3_log(p.q);
   const Dual th = norm3(phi.x, phi.y, phi.z);
+  // c(th) = (1 - (th / 2) cot(th / 2)) / th^2 = 1/12 + th^2/720 + th^4/30240 + th^6/1209600 + th^8/47900160 + ...
+  // The closed form subtracts two numbers near 1: its value carries an absolute error of about eps32 / th^2 and its dual derivative one
+  // of about eps32 / th^3, so below C_SERIES = 0.5 the series is used (through th^6: the first dropped term is 12 th^8 / 4.8e7 < 1e-9
+  // of c there, far below eps32); from 0.5 on the closed form's cancellation is at most 4 eps32 absolute (48 eps32 of c), 8 eps32 in
+  // the derivative.
   Dual c;
-  if (th.v < 1e-4f) {
-    c = cst(1.f / 12.f) + (1.f / 720.f) * (th * th);
+  if (th.v < C_SERIES) {
+    const Dual th2 = th * th;
+    c = cst(1.f / 12.f) + th2 * (cst(1.f / 720.f) + th2 * (cst(1.f / 30240.f) + (1.f / 1209600.f) * th2));
   } else {
     const Dual h = 0.5f * th;
     c = (cst(1.f) - th * dcos(h) / (2.f * dsin(h))) / (th * th);

@@ -11,13 +11,23 @@ RP_DEV void rot(float& a, float& b, float c, float s) {
 }
 
 // one 3x3 SVD in registers: A row-major [9] -> u[col][row], sg[3] descending, v[col][row]
+// Domain: finite float32 entries, the largest of them normal.  A is multiplied at entry by the exact power of two that brings its largest
+// magnitude into [0.5, 1) and sg is scaled back at the end: the squared column norms and their products (alpha beta of the skip test
+// overflows from |A| ~ 4e9 on, the norms go denormal below ~1e-19) then stay in range whatever the scale of A.  Every rotation decision
+// is a ratio of such terms, so a matrix that was in range before gives the same bits with the scaling as without it.  (Entries more
+// than 2^-126 below the largest are flushed by the scaling -- far below its rounding; sg overflows only if sigma_1 itself does.)
 RP_DEV void svd3x3_dev(const float* A, float (&u)[3][3], float (&sg)[3], float (&v)[3][3]) {
   float w[3][3];                       // w[col][row]
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) amax = fmaxf(amax, fabsf(A[i]));
+  int ex = 0;
+  if (amax > 0.f && amax <= 3.402823466e38f) frexpf(amax, &ex);     // a zero (or non-finite) matrix is left as it is
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      w[c][r] = A[3 * r + c];
+      w[c][r] = ldexpf(A[3 * r + c], -ex);
       v[c][r] = r == c ? 1.f : 0.f;
     }
 #pragma unroll 1
@@ -74,4 +84,6 @@ RP_DEV void svd3x3_dev(const float* A, float (&u)[3][3], float (&sg)[3], float (
     u[2][1] = u[0][2] * u[1][0] - u[0][0] * u[1][2];
     u[2][2] = u[0][0] * u[1][1] - u[0][1] * u[1][0];
   }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) sg[c] = ldexpf(sg[c], ex);
 }

@@ -10,6 +10,8 @@ lietorch is UNPINNED (no lietorch here, no test in the reference) -- SURVEY.md 8
 """
 import torch
 
+C_SERIES = 0.5    # below this angle SE3.log takes c(theta) from its series (csrc/se3loss.hip: C_SERIES)
+
 
 def _qmul(a, b):
     ax, ay, az, aw = a.unbind(-1)
@@ -39,7 +41,10 @@ def _so3_log(q):
     w, n_s = w * sign, n
     small = n_s < 1e-6
     n_safe = torch.where(small, torch.ones_like(n_s), n_s)
-    fac = torch.where(small, 2.0 / w.clamp_min(1e-12) - (2.0 / 3.0) * n_s * n_s / w.clamp_min(1e-12) ** 3,
+    # the series side is evaluated everywhere: away from its branch it gets w = 1, or at a half-turn (w = 0) the float32 backward of
+    # 1 / w^3 is inf, and inf times the zero that `where` hands it is NaN
+    w_safe = torch.where(small, w.clamp_min(1e-12), torch.ones_like(w))
+    fac = torch.where(small, 2.0 / w_safe - (2.0 / 3.0) * n_s * n_s / w_safe ** 3,
                       2.0 * torch.atan2(n_safe, w) / n_safe)
     return u * (sign * fac).unsqueeze(-1)
 
@@ -89,9 +94,11 @@ class SE3:
         th = phi.norm(dim=-1)
         K = _hat(phi)
         th2 = th * th
-        small = th < 1e-4
+        # c = (1 - (th / 2) cot(th / 2)) / th^2.  The closed form cancels (absolute error eps / th^2, eps / th^3 in its derivative), so
+        # below C_SERIES the series is used; through th^6 its truncation is below 1e-9 of c there (csrc/se3loss.hip: se3_log_norms).
+        small = th < C_SERIES
         ths = torch.where(small, torch.ones_like(th), th)
-        c = torch.where(small, 1.0 / 12.0 + th2 / 720.0,
+        c = torch.where(small, 1.0 / 12.0 + th2 * (1.0 / 720.0 + th2 * (1.0 / 30240.0 + th2 * (1.0 / 1209600.0))),
                         (1.0 - ths * torch.cos(ths / 2) / (2.0 * torch.sin(ths / 2))) / (ths * ths))
         eye = torch.eye(3, dtype=t.dtype, device=t.device).expand(K.shape)
         Vinv = eye - 0.5 * K + c[..., None, None] * (K @ K)

@@ -50,6 +50,82 @@ def scenes(n, P, seed, max_angle=0.5):
     return x1, x2, E
 
 
+WIDE_KINDS = ("wide", "beyond120", "half_turn", "axis_t")
+MAX_X2 = 3.6         # wide_scenes: the largest image coordinate it accepts (the bounds of the GPU tests assume terms of order 1)
+
+
+def shepperd_branch(R):
+    """which pivot the rotation -> quaternion code takes: 0 the trace (> 0), 1 / 2 / 3 the largest of R00 / R11 / R22"""
+    if R[0, 0] + R[1, 1] + R[2, 2] > 0:
+        return 0
+    if R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        return 1
+    return 2 if R[1, 1] > R[2, 2] else 3
+
+
+def _axis_angle(axis, a):
+    """(R, q xyzw with w >= 0) of a rotation by 0 <= a <= pi about the unit axis; a = pi exactly: R = 2 a a^T - I, w = 0"""
+    if a == np.pi:
+        return 2 * np.outer(axis, axis) - np.eye(3), np.concatenate([axis, [0.0]])
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    return np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K, np.concatenate([axis * np.sin(a / 2), [np.cos(a / 2)]])
+
+
+def wide_scenes(n, P, seed, kind):
+    """n two-view scenes with a wide relative rotation, fp64: x1, x2 [n,P,2], E_true [n,3,3] (singular values 1, 1, 0) and the true pose
+    [n,7] = (t unit, q xyzw with w >= 0), X2 = R X1 + t.  kind:
+      "wide"       angle uniform in 0.5 .. 2.0 rad about a random axis
+      "beyond120"  angle uniform in 2.2 .. 3.1 rad (the trace of R is negative) about e_(b mod 3) + 0.25 N(0, 1): each of the three
+                   non-trace pivots of the rotation -> quaternion conversion is the largest for a third of the problems
+      "half_turn"  angle pi exactly about the same axes, q.w = 0; problems 0, 1, 2 turn about e_0, e_1, e_2 themselves (R diagonal)
+      "axis_t"     a "wide" rotation; even problems have t = +-e_k exactly, odd ones a t whose two smallest magnitudes are equal
+    Points as in `scenes` (2 .. 8 in front of camera 1, |xy| <= 0.55 z); t (0.5 .. 1.5 long) is then lifted along camera 2's axis until
+    every point has z2 >= 2 and moved sideways by half the mean lateral offset of the points in camera 2, so nothing is rejected.
+    "axis_t" cannot move t: its points are a box of side 1.2 centred 8 .. 10 along the bisector of the two optical axes (|t| = 1).
+    Asserted here: every point is in front of both cameras, |x2| <= MAX_X2, and for the two large-angle kinds every non-trace pivot is
+    taken by at least n / 4 problems."""
+    assert kind in WIDE_KINDS, kind
+    rng = np.random.default_rng(1000 * seed + P + 100003 * (1 + WIDE_KINDS.index(kind)))
+    x1, x2, E, pose = np.empty((n, P, 2)), np.empty((n, P, 2)), np.empty((n, 3, 3)), np.empty((n, 7))
+    branch = np.empty(n, int)
+    for b in range(n):
+        if kind in ("wide", "axis_t"):
+            axis, a = rng.standard_normal(3), rng.uniform(0.5, 2.0)
+        else:
+            axis = np.eye(3)[b % 3] + (0.25 * rng.standard_normal(3) if (kind == "beyond120" or b >= 3) else 0.0)
+            a = rng.uniform(2.2, 3.1) if kind == "beyond120" else np.pi
+        axis = axis / np.linalg.norm(axis)
+        R, q = _axis_angle(axis, a)
+        if kind == "axis_t":
+            k, sgn = (b // 2) % 3, 1.0 - 2.0 * ((b // 6) % 2)
+            if b % 2 == 0:
+                t = sgn * np.eye(3)[k]
+            else:
+                small = rng.uniform(0.1, 0.5)
+                t = np.full(3, small) * rng.choice([-1.0, 1.0], 3)
+                t[k] = sgn * np.sqrt(1 - 2 * small * small)
+            d = np.array([0, 0, 1.0]) + R.T[:, 2]                   # the bisector of the optical axes, in camera 1's frame
+            X1 = rng.uniform(8.0, 10.0) * d / np.linalg.norm(d) + rng.uniform(-0.6, 0.6, (P, 3))
+            X2 = X1 @ R.T + t
+        else:
+            t = rng.standard_normal(3)
+            t *= rng.uniform(0.5, 1.5) / np.linalg.norm(t)
+            z = rng.uniform(2.0, 8.0, P)
+            X1 = np.concatenate([rng.uniform(-0.55, 0.55, (P, 2)) * z[:, None], z[:, None]], -1)
+            Xr = X1 @ R.T
+            t[2] += max(0.0, 2.0 - (Xr[:, 2] + t[2]).min())
+            t[:2] -= 0.5 * (Xr[:, :2] + t[:2]).mean(0)
+            X2 = Xr + t
+        assert X1[:, 2].min() > 0.5 and X2[:, 2].min() > 0.5, (kind, b)
+        x1[b], x2[b], E[b] = X1[:, :2] / X1[:, 2:], X2[:, :2] / X2[:, 2:], true_essential(R, t)
+        pose[b] = np.concatenate([t / np.linalg.norm(t), q])
+        branch[b] = shepperd_branch(R)
+    assert np.abs(x2).max() <= MAX_X2 and np.abs(x1).max() <= MAX_X2, (kind, np.abs(x1).max(), np.abs(x2).max())
+    if kind in ("beyond120", "half_turn"):
+        assert all(int((branch == k).sum()) >= n // 4 for k in (1, 2, 3)), np.bincount(branch, minlength=4)
+    return x1, x2, E, pose
+
+
 def noisy_scene(seed, P=576, outliers=0.1, sigma=1e-3):
     """one wide-baseline scene (|t| 1 .. 1.5 against depths of 2 .. 8, a rotation of up to 0.3 rad) of P points with Gaussian noise of
     `sigma` on both images and a share `outliers` of x2 replaced by uniform noise over the field of view:

@@ -7,13 +7,13 @@
                  bounds are calibrated against it: 8 x its largest error on the same inputs.
   decode_pose    E -> (R, t) by the cheirality vote, fp64 (the counterpart of rp_pose_from_essential), and the helpers around poses:
                  quaternion <-> rotation, the retraction, angles between poses, perturbed starts.
-  scenes / noisy_scene come from tests/_eightpoint_ref.py; scenes_with_pose adds the true pose to `scenes`.
+  scenes / wide_scenes / noisy_scene come from tests/_eightpoint_ref.py; scenes_with_pose adds the true pose to `scenes`.
 """
 import collections
 
 import numpy as np
 
-from tests._eightpoint_ref import EPS32, noisy_scene, scenes  # noqa: F401  (re-exported)
+from tests._eightpoint_ref import EPS32, noisy_scene, scenes, wide_scenes  # noqa: F401  (re-exported)
 
 MIN_NORM = 1e-30     # |t0| or |q0| below this: degenerate
 LAMBDA0, LAMBDA_MIN, LAMBDA_MAX = 1e-3, 1e-7, 1e7

@@ -168,6 +168,48 @@ def test_float32_restatement_is_within_the_perturbation_bound():
             assert float(ratio.max()) <= C_PARITY / 8, (P, weighted, float(ratio.max()))
 
 
+@pytest.mark.parametrize("kind", R.WIDE_KINDS)
+def test_wide_scenes_are_what_they_say(kind):
+    """wide_scenes asserts its own properties (points in front, |x| <= 3.6, every pivot taken); here: the pose it returns is the pose of its
+    E_true and of its points, the angle is in the kind's range, and the eight-point problem is as well conditioned as on `scenes`"""
+    from tests import _refine_ref as F
+    lo, hi = {"wide": (0.5, 2.0), "beyond120": (2.2, 3.1), "half_turn": (np.pi, np.pi), "axis_t": (0.5, 2.0)}[kind]
+    for P, n in ((8, 24), (12, 90), (300, 6)):
+        x1, x2, E, pose = R.wide_scenes(n, P, 3, kind)
+        assert np.abs(np.linalg.svd(E, compute_uv=False) - [1, 1, 0]).max() < 1e-12
+        assert float(np.abs(R.sampson64(E, x1, x2)).max()) < 1e-24
+        angle = 2 * np.arccos(np.clip(pose[:, 6], -1, 1))
+        assert angle.min() >= lo - 1e-12 and angle.max() <= hi + 1e-12 and bool((pose[:, 6] >= 0).all())
+        for b in range(n):
+            got = F.decode_pose(E[b], x1[b], x2[b])
+            flip = np.concatenate([got[:3], -got[3:]])
+            assert min(np.abs(got - pose[b]).max(), np.abs(flip - pose[b]).max()) < 1e-9, (kind, P, b)
+        s8 = R.eight_point_ref(x1, x2)[1][:, 1].min()
+        assert s8 >= (1e-5 if P == 8 else 1e-4 if P == 12 else 5e-3), (kind, P, s8)
+    if kind == "half_turn":
+        assert np.array_equal(pose[:3, 3:6], np.eye(3)) and not pose[:, 6].any()
+    if kind == "axis_t":
+        t = np.abs(pose[:, :3])
+        assert all(sorted(t[b]) == [0, 0, 1] for b in range(0, n, 2)) and all(np.sort(t[b])[0] == np.sort(t[b])[1] > 0 for b in range(1, n, 2))
+
+
+def test_float32_restatement_on_wide_baselines():
+    """the restatement against the reference on tests/test_gpu_eightpoint.py's wide-baseline inputs, whose bounds keep the constants of
+    test_parity.  Measured over all of them: E ratio 2.05 (P = 8, half_turn, weighted; 1.15 otherwise at P = 8, 0.23 .. 0.93 for P >= 64),
+    stat ratio 1.07 (P = 64) -- above C / 8 = 1.37 and 0.93: image coordinates reach 3 here (0.55 on `scenes`), and the bound's "terms of order
+    1" grow with them.  The constants were not raised for it, so the GPU keeps a factor 5 over the restatement here instead of 8; the
+    restatement must stay within C / 4."""
+    from tests.test_gpu_eightpoint import C_PARITY, C_STAT, wide_inputs
+    for kind, P, n in (("beyond120", 8, 60), ("half_turn", 8, 60), ("half_turn", 64, 12)):
+        for weighted in (False, True):
+            x1, x2, w = wide_inputs(kind, P, n, weighted)
+            Er, sr, _ = R.eight_point_ref(x1, x2, w)
+            Ef, sf, _ = R.eight_point_f32(x1, x2, w)
+            scale = R.EPS32 / sr[:, 1]
+            ratio, stat = R.up_to_sign(Ef, Er) / scale, np.abs(sf[:, :3] - sr[:, :3]).max(-1) / scale
+            assert float(ratio.max()) <= C_PARITY / 4 and float(stat.max()) <= C_STAT / 4, (kind, P, weighted, ratio.max(), stat.max())
+
+
 def _hand_made(B=2, H=2):
     """B pairs, H heads: every image's rows follow a permutation of their own; in image 1 of pair 0, head 1, rows 5 and 7 both pick
     the column row 7 owns, so row 5 is not mutual"""

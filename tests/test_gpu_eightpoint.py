@@ -100,6 +100,40 @@ def test_parity(ep, P, n, weighted):
     assert ep.eight_point(dev(x1), dev(x2), dev(w)).weights is None
 
 
+WIDE_CASES = [(8, 60), (64, 12), (300, 6)]
+
+
+@functools.lru_cache(maxsize=None)
+def wide_inputs(kind, P, n, weighted):
+    """parity_inputs on R.wide_scenes: rotations of 2.2 .. 3.1 rad ("beyond120") or of exactly pi ("half_turn")"""
+    x1, x2, _, _ = R.wide_scenes(n, P, 11, kind)
+    w = np.random.default_rng(P + n).uniform(0.05, 1.0, (n, P)).astype(np.float32) if weighted else None
+    return x1.astype(np.float32), x2.astype(np.float32), w
+
+
+@functools.lru_cache(maxsize=None)
+def wide_reference(kind, P, n, weighted):
+    return R.eight_point_ref(*wide_inputs(kind, P, n, weighted))
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["ones", "weighted"])
+@pytest.mark.parametrize("P,n", WIDE_CASES)
+@pytest.mark.parametrize("kind", ["beyond120", "half_turn"])
+def test_parity_wide_baseline(ep, kind, P, n, weighted):
+    """test_parity beyond a rotation of 120 degrees and at a half-turn, same bounds and constants (the restatement's largest ratios on
+    these inputs: E 2.05 at P = 8, 0.93 for P >= 64; stat 1.07 -- tests/test_eightpoint_cpu.py)"""
+    x1, x2, w = wide_inputs(kind, P, n, weighted)
+    Er, sr, _ = wide_reference(kind, P, n, weighted)
+    out = ep.eight_point(dev(x1), dev(x2), dev(w), return_weights=True)
+    assert out.E.shape == (n, 3, 3) and out.stat.shape == (n, 4) and out.weights.shape == (n, P)
+    check_parity("parity_%s_P%d_n%d_%s" % (kind, P, n, "w" if weighted else "ones"), out.E, out.stat, Er, sr)
+    assert torch.equal(out.weights.cpu(), torch.ones(n, P) if w is None else torch.from_numpy(w))
+    sv = np.linalg.svd(host(out.E), compute_uv=False)
+    assert np.abs(sv - [1, 1, 0]).max() < 1e-5                    # on the essential manifold
+    again = ep.eight_point(dev(x1), dev(x2), dev(w), return_weights=True)
+    assert all(torch.equal(a, b) for a, b in zip(out, again))     # bit-identical from call to call
+
+
 def test_sign_rule(ep):
     """where the reference's largest entry is at least 10 % above the runner-up the sign is determined: E equals E_ref, not -E_ref"""
     seen = 0

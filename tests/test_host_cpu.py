@@ -286,6 +286,60 @@ def test_se3_algebra_and_loss():
     assert torch.isfinite(est2.grad).all() and float(ltr) > 0
 
 
+def test_so3_log_has_a_finite_float32_gradient_at_an_exact_half_turn():
+    """w = 0: the series side of _so3_log's `where` is not selected, but its backward ran on w.clamp_min(1e-12) ** 3, whose float32
+    derivative is inf, and inf times the zero that `where` hands back is NaN.  The unselected side now gets w = 1."""
+    from rel_pose_amd.se3 import SE3, _so3_log
+    for dtype in (torch.float32, torch.float64):
+        q = torch.tensor([[1.0, 0, 0, 0], [0, 0.6, 0.8, 0], [0.6, 0, 0.8, 0], [0, 0, 0, 1.0], [1e-8, 0, 0, 1.0]], dtype=dtype, requires_grad=True)
+        phi = _so3_log(q)
+        phi.norm(dim=-1).sum().backward()
+        assert torch.isfinite(phi).all() and torch.isfinite(q.grad).all(), (dtype, q.grad)
+        assert torch.allclose(phi.norm(dim=-1)[:3], torch.full((3,), np.pi, dtype=dtype)) and float(phi[3].abs().max()) == 0
+        # d|phi| / dw = -2 n / (n^2 + w^2) = -2 at the half-turn
+        assert torch.allclose(q.grad[:3, 3], torch.full((3,), -2.0, dtype=dtype))
+        assert abs(float(phi[4, 0]) - 2e-8) < 1e-14                  # the series side itself is unchanged
+        d = torch.tensor([[0.3, -1.0, 2.0, 0, 0.6, 0.8, 0]], dtype=dtype, requires_grad=True)
+        SE3(d).log().norm(dim=-1).sum().backward()
+        assert torch.isfinite(d.grad).all()
+
+
+def test_loss_sweep_constants():
+    """tests/_geometry_edges.py: the float32 CPU run of se3.py on the loss sweep reproduces the measurement behind the constants the GPU test uses
+    (each 8 x its worst ratio), is finite everywhere, and with c(theta) from its closed form above 1e-4 -- the parent's threshold --
+    its translation gradient breaks C_TR in theta = 1.1e-4 .. 1e-2 and nowhere else.  The fp64 formulas the gradients are referred to agree
+    with scipy.linalg.logm on every row below the cut."""
+    from rel_pose_amd import se3
+    from rel_pose_amd.losses import geodesic_loss_tensors_torch as loss
+    from tests import _geometry_edges as G
+    Ps, Gs, grid = G.loss_sweep()
+    ref = G.loss_reference()
+    assert len(grid) == 85 and G.LOGM_UP_TO < np.pi - 1e-5
+    nt, nphi, _ = G.loss_terms64(Ps, Gs)
+    low = grid[:, 0] <= G.LOGM_UP_TO
+    assert np.abs(nt.mean(-1) - ref["v_tr"])[low].max() < 1e-10 and np.abs(nphi.mean(-1) - ref["v_rot"])[low].max() < 1e-10   # (1.2e-12, 3.3e-13)
+
+    def ratios():
+        g_tr, g_rot = G.loss_gradients(loss, Ps, Gs)
+        v_tr, v_rot = G.loss_values(loss, Ps, Gs)
+        assert all(np.isfinite(a).all() for a in (g_tr, g_rot, v_tr, v_rot))
+        return G.loss_ratios(g_tr, g_rot, v_tr, v_rot, ref)
+    r_rot, r_tr, r_vtr, r_vrot, kink = ratios()
+    got = [float(np.nanmax(r)) for r in (r_rot, r_tr, r_vtr, r_vrot)]
+    print("float32 se3.py: rot %.3g tr %.3g |tau| %.3g |phi| %.3g kink %.3g" % (*got, kink))
+    for g, C in zip(got, (G.C_ROT, G.C_TR, G.C_VAL_TR, G.C_VAL_ROT)):
+        assert C / 16 <= g <= C / 4, (got, C)            # the constants are 8 x (2.80, 6.51, 2.73, 2.79); another libm may move these a little
+    assert kink <= 1
+    keep = se3.C_SERIES
+    try:
+        se3.C_SERIES = 1e-4
+        old = ratios()[1]
+    finally:
+        se3.C_SERIES = keep
+    band = (grid[:, 0] > 1e-4) & (grid[:, 0] <= 1e-2)
+    assert float(np.nanmax(old[band])) > G.C_TR and float(np.nanmax(old[~band])) <= G.C_TR / 4       # (571; 4.97)
+
+
 def test_lazy_metrics_hand_plain_floats_to_every_dict_consumer():
     """reference train.py:168 does `metrics.update(geo_metrics)` and gives the dict to its Logger: CPython's dict fast paths must
     not copy the pending device tensors out of the subclass."""

@@ -239,6 +239,32 @@ def test_float32_restatement_is_within_the_calibrated_bounds():
             assert float(T.weight_ratio(f0.weights, start, x1, x2, w).max()) <= T.C_W / 8
 
 
+def test_float32_restatement_on_wide_baselines():
+    """refine_f32 against refine_ref on tests/test_gpu_refine.py's wide-baseline inputs (rotations beyond 120 degrees and exact half-turns,
+    where the reference's q.w is 2e-5 .. 3e-3; below 1e-3 the quaternions are compared up to sign), whose bounds keep the constants of the other
+    cases.  The reference accepts its first step in every problem, and 96 .. 100 % converge.  Measured over all of them: one step pose 0.33,
+    E 0.34 (half_turn, P = 64; 0.01 .. 0.08 elsewhere), converged pose 1.37, E 1.39 (P = 8), cost 0.72.  The one-step ratio is above
+    C_STEP / 8 = 0.126: single scenes stand out (image coordinates reach 3 here against 0.55 on `scenes`, so the residual's absolute
+    rounding error is larger against the residual), with the same figures for rotations below 120 degrees.  The constants were not raised
+    for it, so the GPU keeps a factor 3 over the restatement there instead of 8; the restatement must stay within C / 2."""
+    from tests import test_gpu_refine as T
+    for kind, P, n in (("beyond120", 8, 24), ("half_turn", 8, 24), ("half_turn", 64, 6)):
+        for weighted in (False, True):
+            start, x1, x2, w = T.wide_inputs(kind, P, n, weighted)
+            for iters, select, kappa, C in ((1, T.clear_first_step, "kappa0", T.C_STEP), (12, T.converged, "kappa", T.C_CONV)):
+                ref = T.wide_reference(kind, P, n, weighted, iters)
+                ok = select(ref)
+                assert ok.mean() >= 0.8
+                assert iters > 1 or bool((ref.stat[:, 2] == 1).all())
+                f32 = F.refine_f32(start, x1, x2, w, T.TAU, iters)
+                pr, er = T.pose_ratio(f32.pose, f32.E, ref, getattr(ref, kappa))
+                assert float(pr[ok].max()) <= C / 2 and float(er[ok].max()) <= C / 2, (kind, P, weighted, iters, pr[ok].max(), er[ok].max())
+                cr = T.cost_ratio(f32.stat.astype(np.float64), start, f32.pose, x1, x2, w)
+                assert float(cr.max()) <= T.C_COST / 8, (kind, P, weighted, iters, cr.max())
+            if kind == "half_turn":
+                assert float(np.abs(T.wide_reference(kind, P, n, weighted, 12).pose[:, 6]).min()) < 1e-3      # the up-to-sign comparison is in use
+
+
 def test_refine_pose_refuses_bad_shapes_before_touching_a_device():
     from rel_pose_amd import refine
     p, x, w = torch.zeros(3, 7), torch.zeros(3, 64, 2), torch.zeros(3, 64)
