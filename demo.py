@@ -105,7 +105,12 @@ def main(argv=None):
                     help="with --eight_point: also print the pose of the chain started from the best of M seeded minimal eight-point "
                          "hypotheses (rel_pose_amd/consensus.py); with --refine its cost joins the cost line")
     ap.add_argument("--seed", type=int, default=0, help="with --consensus: the seed of its sampler")
+    ap.add_argument("--subtoken", choices=("window", "quadratic"), default=None,
+                    help="with --eight_point or --matches: localise every match between the token centres (rel_pose_amd/readout.py, "
+                         "subtoken_correspondences) -- the poses are then computed from those positions, the .npz also carries them")
     args = ap.parse_args(argv)
+    if args.subtoken and not (args.eight_point or args.matches):
+        ap.error("--subtoken needs --eight_point or --matches")
     if args.consensus and not args.eight_point:
         ap.error("--consensus needs --eight_point")
     if args.consensus < 0:
@@ -140,9 +145,9 @@ def main(argv=None):
         print("predicted R, as quaternion in format qx,qy,qz,qw")
         print(preds[3:])
     if args.matches:
-        write_matches(model, images, args.matches)
+        write_matches(model, images, args.matches, args.subtoken)
     if args.eight_point:
-        print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine, args.consensus, args.seed)
+        print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine, args.consensus, args.seed, args.subtoken)
     return preds
 
 
@@ -161,20 +166,20 @@ def _angles_line(name, p, r):
           % (name, " ".join("%.5f" % v for v in p.tolist()), 2 * np.degrees(np.arccos(dq)), np.degrees(np.arccos(dt))))
 
 
-def print_eight_point(model, images, intr, orig_hw, regressed, refine=0, consensus=0, seed=0):
+def print_eight_point(model, images, intr, orig_hw, regressed, refine=0, consensus=0, seed=0, subtoken=None):
     """--eight_point: one line -- the pose (t unit, q xyzw) the weighted eight-point algorithm finds from the EMM's matches, the angle
     between its rotation and the regressed one, and the angle between the two translation directions, in degrees.  `regressed` is the
     [7] pose this script prints (t, q xyzw); the intrinsics follow the images' resize.  refine = N > 0 (--refine N): one more line of the same
     form for the pose after N refinement iterations, and one with the mean robust Sampson cost of the three poses.  consensus = M > 0
     (--consensus M): one more pose line, the chain started from the best of M hypotheses (refined N times, too); its cost joins the
-    cost line."""
+    cost line.  subtoken = "window" / "quadratic" (--subtoken): every chain and the cost line run on the localised matches."""
     H, W = images.shape[-2:]
     sy, sx = H / orig_hw[0], W / orig_hw[1]
     K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
     r = torch.from_numpy(np.asarray(regressed, dtype=np.float64))
-    cp = model.consensus_pose_from_matches(images, K, hypotheses=consensus, seed=seed, refine=refine) if consensus else None
+    cp = model.consensus_pose_from_matches(images, K, hypotheses=consensus, seed=seed, refine=refine, subtoken=subtoken) if consensus else None
     if not refine:
-        _angles_line("eight-point", model.pose_from_matches(images, K).pose[0].double().cpu(), r)
+        _angles_line("eight-point", model.pose_from_matches(images, K, subtoken=subtoken).pose[0].double().cpu(), r)
         if cp is not None:
             _angles_line("consensus", cp.pose[0].double().cpu(), r)
         return
@@ -183,12 +188,16 @@ def print_eight_point(model, images, intr, orig_hw, regressed, refine=0, consens
     from rel_pose_amd import eightpoint
     from rel_pose_amd import refine as refine_
     hw = (int(H), int(W))
-    rp = model.refined_pose_from_matches(images, K, refine=refine)
+    rp = model.refined_pose_from_matches(images, K, refine=refine, subtoken=subtoken)
     _angles_line("eight-point", rp.initial.pose[0].double().cpu(), r)
     _angles_line("refined", rp.pose[0].double().cpu(), r)
     if cp is not None:
         _angles_line("consensus", cp.pose[0].double().cpu(), r)
-    x1, x2, w = eightpoint.assemble_matches(model.correspondences(images), K, hw)
+    if subtoken is None:
+        x1, x2, w = eightpoint.assemble_matches(model.correspondences(images), K, hw)
+    else:
+        sub = model.subtoken_correspondences(images)
+        x1, x2, w = eightpoint.assemble_matches(sub.corr, K, hw, sub=sub, subtoken=subtoken)
     tau = eightpoint.default_tau(K, hw).contiguous()
     poses = torch.cat([torch.from_numpy(np.asarray(regressed, dtype=np.float32))[None].cuda(), rp.initial.pose, rp.pose])
     cost = refine_.refine_pose(poses, x1.expand(3, -1, -1).contiguous(), x2.expand(3, -1, -1).contiguous(), w.expand(3, -1).contiguous(),
@@ -197,17 +206,25 @@ def print_eight_point(model, images, intr, orig_hw, regressed, refine=0, consens
     print(line if cp is None else line + ", consensus %.6e" % float(cp.stat[0, 1]))
 
 
-def write_matches(model, images, path):
+def write_matches(model, images, path, subtoken=None):
     """--matches: the readout of the pair's EMM attention as an .npz -- row_idx / col_idx [2,3,576], row_stat / col_stat [2,3,576,4],
     mutual [2,3,576] (rel_pose_amd.readout.Correspondences) and, per head h, match_xy0_h<h> / match_xy1_h<h> [M,2] / match_conf_h<h> [M]:
-    pixel centres (of the images as the model saw them) in image 0 / image 1 of the mutual matches of image 1's attention."""
+    pixel centres (of the images as the model saw them) in image 0 / image 1 of the mutual matches of image 1's attention.
+    subtoken = "window" / "quadratic" (--subtoken): also row_win / row_quad / col_win / col_quad [2,3,576,4]
+    (rel_pose_amd.readout.SubtokenCorrespondences) and, per head, match_sub_xy1_h<h> [M,2]: the localised pixel position in image 1."""
     from rel_pose_amd import readout
-    corr = model.correspondences(images)
+    sub = model.subtoken_correspondences(images) if subtoken else None
+    corr = sub.corr if subtoken else model.correspondences(images)
     out = {k: getattr(corr, k).cpu().numpy() for k in ("row_idx", "row_stat", "col_idx", "col_stat", "mutual")}
+    if subtoken:
+        out.update({k: getattr(sub, k).cpu().numpy() for k in ("row_win", "row_quad", "col_win", "col_quad")})
     counts = []
     for h in range(corr.row_idx.shape[1]):
         xy0, xy1, conf = readout.matches_xy(corr, 1, h, images.shape[-2:])
         out["match_xy0_h%d" % h], out["match_xy1_h%d" % h], out["match_conf_h%d" % h] = xy0.cpu().numpy(), xy1.cpu().numpy(), conf.cpu().numpy()
+        if subtoken:
+            pos = (sub.row_win if subtoken == "window" else sub.row_quad)[1, h][corr.mutual[1, h]]
+            out["match_sub_xy1_h%d" % h] = readout.subtoken_xy(pos, images.shape[-2:]).cpu().numpy()
         counts.append(int(xy0.shape[0]))
     np.savez(path, **out)
     print("mutual matches per head: %s -> %s" % (" ".join(str(c) for c in counts), path))

@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so and librelpose_consensus.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so and librelpose_submatch.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -24,6 +24,10 @@ REFINE_SOURCES = ["refine_pose.hip"]
 CONSENSUS_CSRC = os.path.join(HERE, "csrc_consensus")
 CONSENSUS_LIB = os.path.join(HERE, "librelpose_consensus.so")
 CONSENSUS_SOURCES = ["consensus.hip"]
+# the sub-token localisation library (include/relpose_submatch.h): a sixth library, the same pattern
+SUBMATCH_CSRC = os.path.join(HERE, "csrc_submatch")
+SUBMATCH_LIB = os.path.join(HERE, "librelpose_submatch.so")
+SUBMATCH_SOURCES = ["submatch.hip"]
 ARCH = "gfx950"
 
 
@@ -61,10 +65,14 @@ def consensus_needs_build():
     return _stale(CONSENSUS_LIB, CONSENSUS_CSRC, CONSENSUS_SOURCES, _consensus_headers())
 
 
+def submatch_needs_build():
+    return _stale(SUBMATCH_LIB, SUBMATCH_CSRC, SUBMATCH_SOURCES, _submatch_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All five libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All six libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -79,6 +87,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, REFINE_LIB, REFINE_CSRC, REFINE_SOURCES, _refine_headers())
             if force or consensus_needs_build():
                 _build_locked(verbose, force, CONSENSUS_LIB, CONSENSUS_CSRC, CONSENSUS_SOURCES, _consensus_headers())
+            if force or submatch_needs_build():
+                _build_locked(verbose, force, SUBMATCH_LIB, SUBMATCH_CSRC, SUBMATCH_SOURCES, _submatch_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -103,6 +113,10 @@ def _refine_headers():
 
 def _consensus_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_consensus.h")]
+
+
+def _submatch_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_submatch.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

@@ -143,6 +143,15 @@ CONSENSUS_MAX_P, CONSENSUS_MAX_M = _CONSENSUS_CONSTS["RP_CONSENSUS_MAX_P"], _CON
 CONSENSUS_EXPORTS = tuple(_CONSENSUS_PROTOTYPES)
 
 
+# the sub-token localisation library (include/relpose_submatch.h -> librelpose_submatch.so): the same parser, errcheck and RP_E* codes a sixth time
+_SUBMATCH_LIB = None
+SUBMATCH_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_submatch.h")
+with open(SUBMATCH_HEADER) as _f:
+    _SUBMATCH_CONSTS, _, _SUBMATCH_PROTOTYPES, _SUBMATCH_STATUS = _header_contract(_f.read(), "relpose_submatch.h")
+SUBMATCH_ABI_VERSION = _SUBMATCH_CONSTS["RP_SUBMATCH_ABI_VERSION"]
+SUBMATCH_EXPORTS = tuple(_SUBMATCH_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -280,6 +289,32 @@ def load_consensus():
         if name in _CONSENSUS_STATUS:
             fn.errcheck = _raise_on_status
     _CONSENSUS_LIB = lib
+    return lib
+
+
+def load_submatch():
+    """Load (building if absent or stale) and type librelpose_submatch.so.  Raises on any failure: there is no fallback."""
+    global _SUBMATCH_LIB
+    if _SUBMATCH_LIB is not None:
+        return _SUBMATCH_LIB
+    path = _build.SUBMATCH_LIB
+    if _build.submatch_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_submatch_abi_version.restype = c_int
+    if lib.rp_submatch_abi_version() != SUBMATCH_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_submatch_abi_version(), SUBMATCH_ABI_VERSION))
+    for name, (res, args) in _SUBMATCH_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _SUBMATCH_STATUS:
+            fn.errcheck = _raise_on_status
+    _SUBMATCH_LIB = lib
     return lib
 
 

@@ -64,15 +64,14 @@ def eight_point_consensus(x1, x2, w=None, tau=0.01, hypotheses=1024, seed=0, ret
     return Consensus(E, best, stat, wo, hyp_E, hyp_cost, samples)
 
 
-def consensus_pose_from_matches(model, images, intrinsics, heads=(0, 1, 2), hypotheses=1024, seed=0, iters=4, tau=None, refine=10):
+def consensus_pose_from_matches(model, images, intrinsics, heads=(0, 1, 2), hypotheses=1024, seed=0, iters=4, tau=None, refine=10,
+                                subtoken=None, radius=2):
     """ViTEss.consensus_pose_from_matches: the chain of the public pieces and nothing else -- eightpoint.assemble_matches ->
     eight_point_consensus -> eightpoint.eight_point on the consensus weights (tau, iters) -> geom.pose_from_essential ->
-    refine.refine_pose on the BASE weights (tau, refine) -> ConsensusMatchPose."""
+    refine.refine_pose on the BASE weights (tau, refine) -> ConsensusMatchPose.  subtoken, radius: as for eightpoint.pose_from_matches."""
     from . import eightpoint, geom
     from . import refine as refine_
-    corr = model.correspondences(images)
-    hw = tuple(int(s) for s in images.shape[-2:])
-    x1, x2, w = eightpoint.assemble_matches(corr, intrinsics, hw, heads)
+    x1, x2, w, hw = eightpoint._matches_of(model, images, intrinsics, heads, subtoken, radius)
     if tau is None:
         tau = eightpoint.default_tau(intrinsics, hw).to(x1.device).contiguous()
     c = eight_point_consensus(x1, x2, w, tau=tau, hypotheses=hypotheses, seed=seed, return_weights=True)

@@ -53,12 +53,18 @@ def eight_point(x1, x2, w=None, tau=None, iters=0, return_weights=False):
     return EightPoint(E, stat, wo)
 
 
-def assemble_matches(corr, intrinsics, image_hw, heads=(0, 1, 2)):
+SUBTOKEN = ("window", "quadratic")
+
+
+def assemble_matches(corr, intrinsics, image_hw, heads=(0, 1, 2), sub=None, subtoken="window"):
     """readout.Correspondences -> (x1 [B,576 len(heads),2], x2 the same, w [B,576 len(heads)]) for eight_point, head after head.
     For pair b the matches are those of image z = 2b + 1's attention (readout.matches_xy): x1 the normalised centres of all 576 tokens
     of image 0, x2 those of their partners row_idx[z,h] in image 1, w = (A at the match) x (the match is mutual) -- fixed shapes, a
     non-mutual row has weight 0.  intrinsics [B,2,4] = (fx, fy, cx, cy) of image 0 / image 1 in pixels of image_hw = (H, W); it is
-    only read."""
+    only read.  sub: a readout.SubtokenCorrespondences of the same images -- x2 is then the localised position of the match,
+    sub.row_win ("window") or sub.row_quad ("quadratic"), instead of the partner's centre; x1 and w are what they are without it."""
+    if sub is not None and subtoken not in SUBTOKEN:
+        raise ValueError("subtoken must be one of %s" % (SUBTOKEN,))
     B = corr.row_idx.shape[0] // 2
     if tuple(intrinsics.shape) != (B, 2, 4):
         raise ValueError("intrinsics must be [B,2,4] with B = %d pairs" % B)
@@ -67,7 +73,10 @@ def assemble_matches(corr, intrinsics, image_hw, heads=(0, 1, 2)):
     heads = list(heads)
     idx = corr.row_idx[1::2][:, heads].long()                                       # [B,h,576]
     xy1 = c.expand(B, len(heads), *c.shape)
-    xy2 = c[idx]                                                                    # [B,h,576,2]
+    if sub is None:
+        xy2 = c[idx]                                                                # [B,h,576,2]
+    else:
+        xy2 = readout.subtoken_xy((sub.row_win if subtoken == "window" else sub.row_quad)[1::2][:, heads], image_hw).to(dt)
     # readout.normalised slices its intrinsics row along the FIRST axis: coordinates first, [2,B,h,576] against [4,B,1,1]
     k = intrinsics.to(device=dev, dtype=dt).permute(2, 1, 0)[..., None, None]       # [4,2,B,1,1]
     x1 = readout.normalised(xy1.permute(3, 0, 1, 2), k[:, 0]).permute(1, 2, 3, 0)
@@ -79,16 +88,27 @@ def assemble_matches(corr, intrinsics, image_hw, heads=(0, 1, 2)):
 
 def default_tau(intrinsics, image_hw):
     """[B]: half a token pitch of image 0 in normalised units, 0.5 (W / 24) / fx -- the matches are token centres, so that is their
-    quantisation scale"""
+    quantisation scale.  With sub-token matches (assemble_matches(sub=...)) the caller should pass a smaller tau; how much smaller is
+    not known for a trained model."""
     return (0.5 * image_hw[1] / readout.GRID) / intrinsics[:, 0, 0].to(torch.float32)
 
 
-def pose_from_matches(model, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None):
-    """ViTEss.pose_from_matches: images [B,2,3,H,W], intrinsics [B,2,4] in pixels of (H, W) -> MatchPose.  The chain of the public
-    pieces: model.correspondences -> assemble_matches -> eight_point -> geom.pose_from_essential."""
-    corr = model.correspondences(images)
+def _matches_of(model, images, intrinsics, heads, subtoken, radius):
+    """(x1, x2, w, hw) of the pose chains: model.correspondences, or with `subtoken` model.subtoken_correspondences, -> assemble_matches"""
     hw = tuple(int(s) for s in images.shape[-2:])
-    x1, x2, w = assemble_matches(corr, intrinsics, hw, heads)
+    if subtoken is None:
+        return assemble_matches(model.correspondences(images), intrinsics, hw, heads) + (hw,)
+    if subtoken not in SUBTOKEN:
+        raise ValueError("subtoken must be None or one of %s" % (SUBTOKEN,))
+    sub = model.subtoken_correspondences(images, radius)
+    return assemble_matches(sub.corr, intrinsics, hw, heads, sub=sub, subtoken=subtoken) + (hw,)
+
+
+def pose_from_matches(model, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None, subtoken=None, radius=2):
+    """ViTEss.pose_from_matches: images [B,2,3,H,W], intrinsics [B,2,4] in pixels of (H, W) -> MatchPose.  The chain of the public
+    pieces: model.correspondences -> assemble_matches -> eight_point -> geom.pose_from_essential; with subtoken = "window" /
+    "quadratic": model.subtoken_correspondences(images, radius) -> assemble_matches(sub.corr, ..., sub=sub, subtoken=subtoken) -> the same."""
+    x1, x2, w, hw = _matches_of(model, images, intrinsics, heads, subtoken, radius)
     if tau is None:
         tau = default_tau(intrinsics, hw).to(x1.device).contiguous()
     ep = eight_point(x1, x2, w, tau=tau, iters=iters, return_weights=True)

@@ -153,28 +153,41 @@ class ViTEss(nn.Module):
         from . import readout
         return readout.correspondences(self, images, dense)
 
-    def pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None):
+    def subtoken_correspondences_from_map(self, fmap, radius=2):
+        """CNN map [2B,192,24,24] -> readout.SubtokenCorrespondences: correspondences_from_map and, around every row and column match, the
+        position between the token centres -- a soft-argmax over the (2 radius + 1)^2 window and a parabola vertex.  eval() mode only."""
+        from . import readout
+        return readout.subtoken_correspondences_from_map(self, fmap, radius)
+
+    def subtoken_correspondences(self, images, radius=2):
+        """images [B,2,3,H,W] -> readout.SubtokenCorrespondences (see subtoken_correspondences_from_map); changes no module state"""
+        from . import readout
+        return readout.subtoken_correspondences(self, images, radius)
+
+    def pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None, subtoken=None, radius=2):
         """images [B,2,3,H,W], intrinsics [B,2,4] = (fx, fy, cx, cy) in pixels of (H, W) -> eightpoint.MatchPose: the CLASSICAL pose of
         the matches the Essential Matrix Module formed -- correspondences -> weighted eight-point with `iters` rounds of robust
-        re-weighting (tau: its scale; None = half a token pitch) -> E -> (R, t) by the cheirality vote.  eval() mode only; changes no
-        module state and does not write to `intrinsics`."""
+        re-weighting (tau: its scale; None = half a token pitch) -> E -> (R, t) by the cheirality vote.  subtoken = "window" / "quadratic":
+        the matches are localised between the token centres first (subtoken_correspondences with `radius`; pass a smaller tau then).
+        eval() mode only; changes no module state and does not write to `intrinsics`."""
         from . import eightpoint
-        return eightpoint.pose_from_matches(self, images, intrinsics, heads, iters, tau)
+        return eightpoint.pose_from_matches(self, images, intrinsics, heads, iters, tau, subtoken, radius)
 
-    def refined_pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None, refine=10):
+    def refined_pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None, refine=10, subtoken=None, radius=2):
         """pose_from_matches followed by `refine` Levenberg-Marquardt iterations on the robust Sampson cost of the same matches (their base
         weights, the same tau) over the five degrees of freedom of (R, t) -> refine.RefinedMatchPose; its `initial` is what
-        pose_from_matches returns.  eval() mode only; changes no module state and does not write to `intrinsics`."""
+        pose_from_matches returns; subtoken, radius as there.  eval() mode only; changes no module state and does not write to `intrinsics`."""
         from . import refine as refine_
-        return refine_.refined_pose_from_matches(self, images, intrinsics, heads, iters, tau, refine)
+        return refine_.refined_pose_from_matches(self, images, intrinsics, heads, iters, tau, refine, subtoken, radius)
 
-    def consensus_pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), hypotheses=1024, seed=0, iters=4, tau=None, refine=10):
+    def consensus_pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), hypotheses=1024, seed=0, iters=4, tau=None, refine=10,
+                                    subtoken=None, radius=2):
         """refined_pose_from_matches started from a consensus instead of the all-data solve: `hypotheses` minimal eight-point samples drawn
         from `seed`, each scored on all matches; the best one's Cauchy weights are the base weights of the eight-point solve that the
         refinement (on the matches' own base weights) then starts from -> consensus.ConsensusMatchPose.  The same seed gives the same
-        bits.  eval() mode only; changes no module state and does not write to `intrinsics`."""
+        bits.  subtoken, radius as for pose_from_matches.  eval() mode only; changes no module state and does not write to `intrinsics`."""
         from . import consensus
-        return consensus.consensus_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, iters, tau, refine)
+        return consensus.consensus_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, iters, tau, refine, subtoken, radius)
 
     def forward(self, images, Gs, intrinsics=None, inference=False):
         if not hasattr(Gs, "data") or isinstance(Gs, np.ndarray):

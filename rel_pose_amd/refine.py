@@ -53,13 +53,11 @@ def refine_pose(pose0, x1, x2, w=None, tau=0.01, iters=10, return_weights=False)
     return RefinedPose(pose, E, stat, wo)
 
 
-def refined_pose_from_matches(model, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None, refine=10):
+def refined_pose_from_matches(model, images, intrinsics, heads=(0, 1, 2), iters=4, tau=None, refine=10, subtoken=None, radius=2):
     """ViTEss.refined_pose_from_matches: the chain of eightpoint.pose_from_matches and, behind it, refine_pose on the same matches with
-    their BASE weights and the same tau."""
+    their BASE weights and the same tau.  subtoken, radius: as for eightpoint.pose_from_matches."""
     from . import eightpoint, geom
-    corr = model.correspondences(images)
-    hw = tuple(int(s) for s in images.shape[-2:])
-    x1, x2, w = eightpoint.assemble_matches(corr, intrinsics, hw, heads)
+    x1, x2, w, hw = eightpoint._matches_of(model, images, intrinsics, heads, subtoken, radius)
     if tau is None:
         tau = eightpoint.default_tau(intrinsics, hw).to(x1.device).contiguous()
     ep = eightpoint.eight_point(x1, x2, w, tau=tau, iters=iters, return_weights=True)
