@@ -105,6 +105,9 @@ def main(argv=None):
                     help="with --eight_point: also print the pose of the chain started from the best of M seeded minimal eight-point "
                          "hypotheses (rel_pose_amd/consensus.py); with --refine its cost joins the cost line")
     ap.add_argument("--seed", type=int, default=0, help="with --consensus: the seed of its sampler")
+    ap.add_argument("--minimal", choices=("eight", "five"), default=None,
+                    help="with --consensus: the minimal solver of its hypotheses -- eight matches (the default) or five, solved by the "
+                         "calibrated five-point solver (rel_pose_amd/fivepoint.py)")
     ap.add_argument("--subtoken", choices=("window", "quadratic"), default=None,
                     help="with --eight_point or --matches: localise every match between the token centres (rel_pose_amd/readout.py, "
                          "subtoken_correspondences) -- the poses are then computed from those positions, the .npz also carries them")
@@ -113,6 +116,8 @@ def main(argv=None):
         ap.error("--subtoken needs --eight_point or --matches")
     if args.consensus and not args.eight_point:
         ap.error("--consensus needs --eight_point")
+    if args.minimal and not args.consensus:
+        ap.error("--minimal needs --consensus")
     if args.consensus < 0:
         ap.error("--consensus takes a positive number of hypotheses")
     if args.refine and not args.eight_point:
@@ -147,7 +152,7 @@ def main(argv=None):
     if args.matches:
         write_matches(model, images, args.matches, args.subtoken)
     if args.eight_point:
-        print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine, args.consensus, args.seed, args.subtoken)
+        print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine, args.consensus, args.seed, args.subtoken, args.minimal or "eight")
     return preds
 
 
@@ -166,18 +171,19 @@ def _angles_line(name, p, r):
           % (name, " ".join("%.5f" % v for v in p.tolist()), 2 * np.degrees(np.arccos(dq)), np.degrees(np.arccos(dt))))
 
 
-def print_eight_point(model, images, intr, orig_hw, regressed, refine=0, consensus=0, seed=0, subtoken=None):
+def print_eight_point(model, images, intr, orig_hw, regressed, refine=0, consensus=0, seed=0, subtoken=None, minimal="eight"):
     """--eight_point: one line -- the pose (t unit, q xyzw) the weighted eight-point algorithm finds from the EMM's matches, the angle
     between its rotation and the regressed one, and the angle between the two translation directions, in degrees.  `regressed` is the
     [7] pose this script prints (t, q xyzw); the intrinsics follow the images' resize.  refine = N > 0 (--refine N): one more line of the same
     form for the pose after N refinement iterations, and one with the mean robust Sampson cost of the three poses.  consensus = M > 0
     (--consensus M): one more pose line, the chain started from the best of M hypotheses (refined N times, too); its cost joins the
-    cost line.  subtoken = "window" / "quadratic" (--subtoken): every chain and the cost line run on the localised matches."""
+    cost line; minimal = "five" (--minimal five): its hypotheses come from the five-point solver.  subtoken = "window" / "quadratic" (--subtoken): every chain and the cost line run on the localised matches."""
     H, W = images.shape[-2:]
     sy, sx = H / orig_hw[0], W / orig_hw[1]
     K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
     r = torch.from_numpy(np.asarray(regressed, dtype=np.float64))
-    cp = model.consensus_pose_from_matches(images, K, hypotheses=consensus, seed=seed, refine=refine, subtoken=subtoken) if consensus else None
+    cp = model.consensus_pose_from_matches(images, K, hypotheses=consensus, seed=seed, refine=refine, subtoken=subtoken,
+                                           minimal=minimal) if consensus else None
     if not refine:
         _angles_line("eight-point", model.pose_from_matches(images, K, subtoken=subtoken).pose[0].double().cpu(), r)
         if cp is not None:

@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so and librelpose_submatch.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so and librelpose_fivepoint.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -28,6 +28,10 @@ CONSENSUS_SOURCES = ["consensus.hip"]
 SUBMATCH_CSRC = os.path.join(HERE, "csrc_submatch")
 SUBMATCH_LIB = os.path.join(HERE, "librelpose_submatch.so")
 SUBMATCH_SOURCES = ["submatch.hip"]
+# the five-point consensus library (include/relpose_fivepoint.h): a seventh library, the same pattern
+FIVEPOINT_CSRC = os.path.join(HERE, "csrc_fivepoint")
+FIVEPOINT_LIB = os.path.join(HERE, "librelpose_fivepoint.so")
+FIVEPOINT_SOURCES = ["five_point.hip"]
 ARCH = "gfx950"
 
 
@@ -69,10 +73,14 @@ def submatch_needs_build():
     return _stale(SUBMATCH_LIB, SUBMATCH_CSRC, SUBMATCH_SOURCES, _submatch_headers())
 
 
+def fivepoint_needs_build():
+    return _stale(FIVEPOINT_LIB, FIVEPOINT_CSRC, FIVEPOINT_SOURCES, _fivepoint_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All six libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All seven libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -89,6 +97,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, CONSENSUS_LIB, CONSENSUS_CSRC, CONSENSUS_SOURCES, _consensus_headers())
             if force or submatch_needs_build():
                 _build_locked(verbose, force, SUBMATCH_LIB, SUBMATCH_CSRC, SUBMATCH_SOURCES, _submatch_headers())
+            if force or fivepoint_needs_build():
+                _build_locked(verbose, force, FIVEPOINT_LIB, FIVEPOINT_CSRC, FIVEPOINT_SOURCES, _fivepoint_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -117,6 +127,10 @@ def _consensus_headers():
 
 def _submatch_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_submatch.h")]
+
+
+def _fivepoint_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_fivepoint.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

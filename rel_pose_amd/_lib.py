@@ -152,6 +152,16 @@ SUBMATCH_ABI_VERSION = _SUBMATCH_CONSTS["RP_SUBMATCH_ABI_VERSION"]
 SUBMATCH_EXPORTS = tuple(_SUBMATCH_PROTOTYPES)
 
 
+# the five-point consensus library (include/relpose_fivepoint.h -> librelpose_fivepoint.so): the same parser, errcheck and RP_E* codes a seventh time
+_FIVEPOINT_LIB = None
+FIVEPOINT_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_fivepoint.h")
+with open(FIVEPOINT_HEADER) as _f:
+    _FIVEPOINT_CONSTS, _, _FIVEPOINT_PROTOTYPES, _FIVEPOINT_STATUS = _header_contract(_f.read(), "relpose_fivepoint.h")
+FIVEPOINT_ABI_VERSION = _FIVEPOINT_CONSTS["RP_FIVEPOINT_ABI_VERSION"]
+FIVEPOINT_MAX_P, FIVEPOINT_MAX_M, FIVEPOINT_ROOTS = (_FIVEPOINT_CONSTS[k] for k in ("RP_FIVEPOINT_MAX_P", "RP_FIVEPOINT_MAX_M", "RP_FIVEPOINT_ROOTS"))
+FIVEPOINT_EXPORTS = tuple(_FIVEPOINT_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -315,6 +325,32 @@ def load_submatch():
         if name in _SUBMATCH_STATUS:
             fn.errcheck = _raise_on_status
     _SUBMATCH_LIB = lib
+    return lib
+
+
+def load_fivepoint():
+    """Load (building if absent or stale) and type librelpose_fivepoint.so.  Raises on any failure: there is no fallback."""
+    global _FIVEPOINT_LIB
+    if _FIVEPOINT_LIB is not None:
+        return _FIVEPOINT_LIB
+    path = _build.FIVEPOINT_LIB
+    if _build.fivepoint_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_fivepoint_abi_version.restype = c_int
+    if lib.rp_fivepoint_abi_version() != FIVEPOINT_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_fivepoint_abi_version(), FIVEPOINT_ABI_VERSION))
+    for name, (res, args) in _FIVEPOINT_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _FIVEPOINT_STATUS:
+            fn.errcheck = _raise_on_status
+    _FIVEPOINT_LIB = lib
     return lib
 
 

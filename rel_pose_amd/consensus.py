@@ -65,16 +65,22 @@ def eight_point_consensus(x1, x2, w=None, tau=0.01, hypotheses=1024, seed=0, ret
 
 
 def consensus_pose_from_matches(model, images, intrinsics, heads=(0, 1, 2), hypotheses=1024, seed=0, iters=4, tau=None, refine=10,
-                                subtoken=None, radius=2):
+                                subtoken=None, radius=2, minimal="eight"):
     """ViTEss.consensus_pose_from_matches: the chain of the public pieces and nothing else -- eightpoint.assemble_matches ->
-    eight_point_consensus -> eightpoint.eight_point on the consensus weights (tau, iters) -> geom.pose_from_essential ->
+    eight_point_consensus (minimal = "five": fivepoint.five_point_consensus, whose FivePointConsensus is then `consensus`) -> eightpoint.eight_point on the consensus weights (tau, iters) -> geom.pose_from_essential ->
     refine.refine_pose on the BASE weights (tau, refine) -> ConsensusMatchPose.  subtoken, radius: as for eightpoint.pose_from_matches."""
     from . import eightpoint, geom
     from . import refine as refine_
+    if minimal not in ("eight", "five"):
+        raise ValueError('minimal must be "eight" or "five"')
     x1, x2, w, hw = eightpoint._matches_of(model, images, intrinsics, heads, subtoken, radius)
     if tau is None:
         tau = eightpoint.default_tau(intrinsics, hw).to(x1.device).contiguous()
-    c = eight_point_consensus(x1, x2, w, tau=tau, hypotheses=hypotheses, seed=seed, return_weights=True)
+    if minimal == "five":
+        from . import fivepoint
+        c = fivepoint.five_point_consensus(x1, x2, w, tau=tau, hypotheses=hypotheses, seed=seed, return_weights=True)
+    else:
+        c = eight_point_consensus(x1, x2, w, tau=tau, hypotheses=hypotheses, seed=seed, return_weights=True)
     ep = eightpoint.eight_point(x1, x2, c.weights, tau=tau, iters=iters, return_weights=True)
     pose, count = geom.pose_from_essential(ep.E, x1, x2)
     r = refine_.refine_pose(pose, x1, x2, w, tau=tau, iters=refine, return_weights=True)

@@ -181,13 +181,16 @@ class ViTEss(nn.Module):
         return refine_.refined_pose_from_matches(self, images, intrinsics, heads, iters, tau, refine, subtoken, radius)
 
     def consensus_pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), hypotheses=1024, seed=0, iters=4, tau=None, refine=10,
-                                    subtoken=None, radius=2):
+                                    subtoken=None, radius=2, minimal="eight"):
         """refined_pose_from_matches started from a consensus instead of the all-data solve: `hypotheses` minimal eight-point samples drawn
         from `seed`, each scored on all matches; the best one's Cauchy weights are the base weights of the eight-point solve that the
         refinement (on the matches' own base weights) then starts from -> consensus.ConsensusMatchPose.  The same seed gives the same
-        bits.  subtoken, radius as for pose_from_matches.  eval() mode only; changes no module state and does not write to `intrinsics`."""
+        bits.  subtoken, radius as for pose_from_matches.  minimal = "five": samples of five matches solved by the calibrated five-point
+        solver (rel_pose_amd/fivepoint.py), which holds up to 60 % of outliers.  eval() mode only; changes no module state and does not
+        write to `intrinsics`."""
         from . import consensus
-        return consensus.consensus_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, iters, tau, refine, subtoken, radius)
+        return consensus.consensus_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, iters, tau, refine, subtoken, radius,
+                                                     minimal)
 
     def forward(self, images, Gs, intrinsics=None, inference=False):
         if not hasattr(Gs, "data") or isinstance(Gs, np.ndarray):
