@@ -9,7 +9,9 @@ These tests check VALUES.  Where a kernel writes, that it writes all of its outp
 held before (guard bands, poisoned outputs, strided layouts) is the memory contract: tests/test_gpu_memory_contract.py over the
 case table of tests/_contract_cases.py.  (The attention launchers read their RP_ATTN_FWD / RP_ATTN_NW overrides once per process, so
 test_attention_fwd_bwd[2] only selects the two-wave workgroups when it is the first attention launch of the process; the two-wave
-forms are reached by size in test_attention_stored_p_fwd_bwd[30], the full-size tests and the Z = 20 cases of the contract table.)
+forms are reached by size in test_attention_stored_p_fwd_bwd[30], the full-size tests and the Z = 20 cases of the contract table, and
+are value-tested by size -- forward, stored-P, recompute and cross backward, per 32-row block and per head against fp64 in peaked, flat,
+climbing and large softmax regimes -- by the Z = 20 cases of tests/test_gpu_softmax_regimes.py.)
 """
 import math
 import os
