@@ -199,14 +199,15 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c128_f32_kernel(CvG p) {
       float* o = p.y + (((long long)g0 + orow[j]) * IW + ocol[j]) * p.CO + 64 * cg + 16 * wave + 4 * kq;
       st4(o, make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]));
     }
-    if (p.stats) {                                            // (wave-uniform) fp32 over the tile's seven pixels, double across tiles
+    if (p.stats) {                                            // (wave-uniform) in double from the first addition: see conv3x3_f32.hip
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float a = 0.f, q = 0.f;
 #pragma unroll
-        for (int j = 0; j < NBLK; ++j) { a += acc[j][e]; q = fmaf(acc[j][e], acc[j][e], q); }
-        sd1[e] += (double)a;
-        sd2[e] += (double)q;
+        for (int j = 0; j < NBLK; ++j) {
+          const double v = (double)acc[j][e];
+          sd1[e] += v;
+          sd2[e] = fma(v, v, sd2[e]);
+        }
       }
     }
     if (t + 1 < t1) {

@@ -203,6 +203,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_f32_kernel(CvF p) {
     });
     // D[m = co 4 kq + e][n = pixel l15]: four consecutive output channels of one pixel per lane.  The epilogue's two sums per channel: y and
     // y^2 (forward: BatchNorm statistics of the output), or -- bn -- g and g * xhat of the masked gradient g (the BatchNorm's backward sums);
+    // the statistics in double from the first addition (an fp32 product is exact in double): summed about zero in fp32, even over seven
+    // pixels, a channel loses its variance below eps32 mean^2 -- a constant channel its rstd; the backward sums (bn) are centred and keep
     // fp32 over the tile's seven pixels, double across tiles
     float ta[4] = {0.f, 0.f, 0.f, 0.f}, tq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -221,12 +223,18 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c64_f32_kernel(CvF p) {
           tq[e] = fmaf(acc[j][e], d * brs[e], tq[e]);
         }
       } else {
+        if (p.stats) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { ta[e] += acc[j][e]; tq[e] = fmaf(acc[j][e], acc[j][e], tq[e]); }
+          for (int e = 0; e < 4; ++e) {
+            const double v = (double)acc[j][e];
+            sd1[e] += v;
+            sd2[e] = fma(v, v, sd2[e]);
+          }
+        }
       }
       st4(p.y + off, make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]));
     }
-    if (p.stats) {                                            // (wave-uniform)
+    if constexpr (BN) {                                       // (stats is set: the host checks it)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         sd1[e] += (double)ta[e];

@@ -147,7 +147,8 @@ __global__ __launch_bounds__(NT, 3) void linear_rows_kernel(RowsP p) {
       for (int t = 0; t < 12; ++t) s += (xn[4 * t] + xn[4 * t + 1]) + (xn[4 * t + 2] + xn[4 * t + 3]);
       s += __shfl_xor(s, 16, 64);
       s += __shfl_xor(s, 32, 64);
-      const float mu = s * (1.0f / C);
+      float mu = s * (1.0f / C);
+      asm volatile("" : "+v"(mu));      // the ROUNDED mean in x - mu, not the product contracted into it (rowwise.hip: ln_fwd_kernel)
       float var = 0.f;
 #pragma unroll
       for (int i = 0; i < 48; ++i) {

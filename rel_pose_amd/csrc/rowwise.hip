@@ -29,7 +29,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     v[j] = xr[lane + 64 * j];
     s += v[j];
   }
-  const float mu = wave_sum(s) * (1.0f / C);
+  float mu = wave_sum(s) * (1.0f / C);
+  // keep the ROUNDED mean: contracted into v - mu the product stays unrounded, so the variance and the output are taken about another
+  // mean than the stored one and a constant row (v - mu = 0 exactly) does not return beta
+  asm volatile("" : "+v"(mu));
   float q = 0.f;
 #pragma unroll
   for (int j = 0; j < J; ++j) {
