@@ -108,6 +108,10 @@ def main(argv=None):
     ap.add_argument("--minimal", choices=("eight", "five"), default=None,
                     help="with --consensus: the minimal solver of its hypotheses -- eight matches (the default) or five, solved by the "
                          "calibrated five-point solver (rel_pose_amd/fivepoint.py)")
+    ap.add_argument("--planar", action="store_true",
+                    help="with --eight_point: also solve the scene as ONE PLANE (rel_pose_amd/homography.py) -- the homography's inlier share "
+                         "next to the essential chain's, the candidates of its decomposition with visibility and Sampson cost, and which "
+                         "one is picked and why; --consensus M and --seed S set its hypotheses (default 256) and its sampler")
     ap.add_argument("--subtoken", choices=("window", "quadratic"), default=None,
                     help="with --eight_point or --matches: localise every match between the token centres (rel_pose_amd/readout.py, "
                          "subtoken_correspondences) -- the poses are then computed from those positions, the .npz also carries them")
@@ -116,6 +120,8 @@ def main(argv=None):
         ap.error("--subtoken needs --eight_point or --matches")
     if args.consensus and not args.eight_point:
         ap.error("--consensus needs --eight_point")
+    if args.planar and not args.eight_point:
+        ap.error("--planar needs --eight_point")
     if args.minimal and not args.consensus:
         ap.error("--minimal needs --consensus")
     if args.consensus < 0:
@@ -153,6 +159,8 @@ def main(argv=None):
         write_matches(model, images, args.matches, args.subtoken)
     if args.eight_point:
         print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine, args.consensus, args.seed, args.subtoken, args.minimal or "eight")
+        if args.planar:
+            print_planar(model, images, intr, png_size(args.img1), args.consensus or 256, args.seed, args.subtoken)
     return preds
 
 
@@ -210,6 +218,35 @@ def print_eight_point(model, images, intr, orig_hw, regressed, refine=0, consens
                                tau=tau.expand(3).contiguous(), iters=0).stat[:, 0].cpu().tolist()
     line = "mean robust Sampson cost of the matches: regressed %.6e, eight-point %.6e, refined %.6e" % tuple(cost)
     print(line if cp is None else line + ", consensus %.6e" % float(cp.stat[0, 1]))
+
+
+def print_planar(model, images, intr, orig_hw, hypotheses=256, seed=0, subtoken=None):
+    """--planar: the scene solved as one plane.  One line with the inlier weight share of the refined homography next to that of the
+    essential chain (eight-point consensus, the same hypotheses and seed) -- no automatic choice between the two models is made: the
+    caller decides --, one line per valid candidate of the decomposition (pose, plane normal, visibility share, robust Sampson cost,
+    |t|/d), and one saying which candidate is picked and why."""
+    H, W = images.shape[-2:]
+    sy, sx = H / orig_hw[0], W / orig_hw[1]
+    K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
+    pp = model.planar_pose_from_matches(images, K, hypotheses=hypotheses, seed=seed, subtoken=subtoken, prior="regressed")
+    cp = model.consensus_pose_from_matches(images, K, hypotheses=hypotheses, seed=seed, refine=0, subtoken=subtoken)
+    print("inlier weight share: homography %.4f (robust transfer cost %.6e), essential matrix %.4f"
+          % (float(pp.stat[0, 1]), float(pp.stat[0, 0]), float(cp.consensus.stat[0, 1])))
+    cs, pick = pp.candidates.cstat[0].cpu(), pp.pick[0].cpu().tolist()
+    for k in range(4):
+        if cs[k, 3] == 1:
+            print("planar candidate %d pose x,y,z,qx,qy,qz,qw: %s ; normal %s ; visibility %.4f, Sampson cost %.6e, |t|/d %.4f"
+                  % (k, " ".join("%.5f" % v for v in pp.candidates.pose[0, k].cpu().tolist()),
+                     " ".join("%.4f" % v for v in pp.candidates.normal[0, k].cpu().tolist()), cs[k, 0], cs[k, 1], cs[k, 2]))
+    if pick[0] < 0:
+        print("planar: no candidate")
+    elif cs[pick[0], 2] == 0:
+        print("planar: candidate 0, a pure rotation (or a plane at infinity)")
+    elif bool(pp.ambiguous[0]):
+        print("planar: candidates %d and %d both see every match; %d is nearer the regressed pose" % (pick[0], pick[1], pick[0]))
+    else:
+        print("planar: candidate %d, %s" % (pick[0], "the only one that sees the plane from both cameras" if cs[pick[0], 0] >= 0.99
+                                             else "by Sampson cost: none sees every match"))
 
 
 def write_matches(model, images, path, subtoken=None):

@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so and librelpose_fivepoint.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so and librelpose_homography.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -32,6 +32,10 @@ SUBMATCH_SOURCES = ["submatch.hip"]
 FIVEPOINT_CSRC = os.path.join(HERE, "csrc_fivepoint")
 FIVEPOINT_LIB = os.path.join(HERE, "librelpose_fivepoint.so")
 FIVEPOINT_SOURCES = ["five_point.hip"]
+# the homography library (include/relpose_homography.h): an eighth library, the same pattern
+HOMOGRAPHY_CSRC = os.path.join(HERE, "csrc_homography")
+HOMOGRAPHY_LIB = os.path.join(HERE, "librelpose_homography.so")
+HOMOGRAPHY_SOURCES = ["homography.hip"]
 ARCH = "gfx950"
 
 
@@ -77,10 +81,14 @@ def fivepoint_needs_build():
     return _stale(FIVEPOINT_LIB, FIVEPOINT_CSRC, FIVEPOINT_SOURCES, _fivepoint_headers())
 
 
+def homography_needs_build():
+    return _stale(HOMOGRAPHY_LIB, HOMOGRAPHY_CSRC, HOMOGRAPHY_SOURCES, _homography_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All seven libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All eight libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -99,6 +107,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, SUBMATCH_LIB, SUBMATCH_CSRC, SUBMATCH_SOURCES, _submatch_headers())
             if force or fivepoint_needs_build():
                 _build_locked(verbose, force, FIVEPOINT_LIB, FIVEPOINT_CSRC, FIVEPOINT_SOURCES, _fivepoint_headers())
+            if force or homography_needs_build():
+                _build_locked(verbose, force, HOMOGRAPHY_LIB, HOMOGRAPHY_CSRC, HOMOGRAPHY_SOURCES, _homography_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -131,6 +141,10 @@ def _submatch_headers():
 
 def _fivepoint_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_fivepoint.h")]
+
+
+def _homography_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_homography.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

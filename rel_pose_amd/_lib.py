@@ -162,6 +162,16 @@ FIVEPOINT_MAX_P, FIVEPOINT_MAX_M, FIVEPOINT_ROOTS = (_FIVEPOINT_CONSTS[k] for k 
 FIVEPOINT_EXPORTS = tuple(_FIVEPOINT_PROTOTYPES)
 
 
+# the homography library (include/relpose_homography.h -> librelpose_homography.so): the same parser, errcheck and RP_E* codes an eighth time
+_HOMOGRAPHY_LIB = None
+HOMOGRAPHY_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_homography.h")
+with open(HOMOGRAPHY_HEADER) as _f:
+    _HOMOGRAPHY_CONSTS, _, _HOMOGRAPHY_PROTOTYPES, _HOMOGRAPHY_STATUS = _header_contract(_f.read(), "relpose_homography.h")
+HOMOGRAPHY_ABI_VERSION = _HOMOGRAPHY_CONSTS["RP_HOMOGRAPHY_ABI_VERSION"]
+HOMOGRAPHY_MAX_P, HOMOGRAPHY_MAX_M, HOMOGRAPHY_MAX_ITERS = (_HOMOGRAPHY_CONSTS[k] for k in ("RP_HOMOGRAPHY_MAX_P", "RP_HOMOGRAPHY_MAX_M", "RP_HOMOGRAPHY_MAX_ITERS"))
+HOMOGRAPHY_EXPORTS = tuple(_HOMOGRAPHY_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -351,6 +361,32 @@ def load_fivepoint():
         if name in _FIVEPOINT_STATUS:
             fn.errcheck = _raise_on_status
     _FIVEPOINT_LIB = lib
+    return lib
+
+
+def load_homography():
+    """Load (building if absent or stale) and type librelpose_homography.so.  Raises on any failure: there is no fallback."""
+    global _HOMOGRAPHY_LIB
+    if _HOMOGRAPHY_LIB is not None:
+        return _HOMOGRAPHY_LIB
+    path = _build.HOMOGRAPHY_LIB
+    if _build.homography_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_homography_abi_version.restype = c_int
+    if lib.rp_homography_abi_version() != HOMOGRAPHY_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_homography_abi_version(), HOMOGRAPHY_ABI_VERSION))
+    for name, (res, args) in _HOMOGRAPHY_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _HOMOGRAPHY_STATUS:
+            fn.errcheck = _raise_on_status
+    _HOMOGRAPHY_LIB = lib
     return lib
 
 

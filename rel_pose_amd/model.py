@@ -192,6 +192,18 @@ class ViTEss(nn.Module):
         return consensus.consensus_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, iters, tau, refine, subtoken, radius,
                                                      minimal)
 
+    def planar_pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), hypotheses=256, seed=0, refine=10, tau=None, subtoken=None,
+                                 radius=2, vis_min=0.99, prior=None):
+        """The pose of a PLANAR scene from the matches, where every essential-matrix chain above fails (two essential matrices fit one
+        plane): `hypotheses` four-point homography samples drawn from `seed`, each scored on all matches; the best one polished by
+        `refine` Levenberg-Marquardt iterations on the robust transfer cost; the closed-form decomposition into at most two physically
+        possible (R, t, n), ranked by visibility (share >= vis_min) and robust Sampson cost -> homography.PlanarMatchPose, whose
+        `ambiguous` says that a second candidate also passes.  prior = "regressed" orders such a pair by distance to the regressed pose.
+        The same seed gives the same bits.  eval() mode only; changes no module state and does not write to `intrinsics`."""
+        from . import homography
+        return homography.planar_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, refine, tau, subtoken, radius, vis_min,
+                                                   prior)
+
     def forward(self, images, Gs, intrinsics=None, inference=False):
         if not hasattr(Gs, "data") or isinstance(Gs, np.ndarray):
             Gs = SE3(torch.from_numpy(np.asarray(Gs)).unsqueeze(0).to(images.device).float())
