@@ -115,7 +115,14 @@ def main(argv=None):
     ap.add_argument("--subtoken", choices=("window", "quadratic"), default=None,
                     help="with --eight_point or --matches: localise every match between the token centres (rel_pose_amd/readout.py, "
                          "subtoken_correspondences) -- the poses are then computed from those positions, the .npz also carries them")
+    ap.add_argument("--points", metavar="OUT.ply", default="",
+                    help="with --eight_point: triangulate the matches under the classical pose (rel_pose_amd/triangulate.py; the refined "
+                         "chain, or with --consensus M the consensus chain) -- an ASCII PLY of the points in front of both cameras whose "
+                         "Cauchy weight is at least 0.5, coloured from image 1, and one line with the reprojection cost, the front share "
+                         "and the mean parallax; OUT.npz writes the arrays instead")
     args = ap.parse_args(argv)
+    if args.points and not args.eight_point:
+        ap.error("--points needs --eight_point")
     if args.subtoken and not (args.eight_point or args.matches):
         ap.error("--subtoken needs --eight_point or --matches")
     if args.consensus and not args.eight_point:
@@ -161,6 +168,9 @@ def main(argv=None):
         print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine, args.consensus, args.seed, args.subtoken, args.minimal or "eight")
         if args.planar:
             print_planar(model, images, intr, png_size(args.img1), args.consensus or 256, args.seed, args.subtoken)
+        if args.points:
+            write_points(model, images, intr, png_size(args.img1), args.points, args.refine or 10, args.consensus, args.seed, args.subtoken,
+                         args.minimal or "eight")
     return preds
 
 
@@ -247,6 +257,38 @@ def print_planar(model, images, intr, orig_hw, hypotheses=256, seed=0, subtoken=
     else:
         print("planar: candidate %d, %s" % (pick[0], "the only one that sees the plane from both cameras" if cs[pick[0], 0] >= 0.99
                                              else "by Sampson cost: none sees every match"))
+
+
+def write_points(model, images, intr, orig_hw, path, refine=10, consensus=0, seed=0, subtoken=None, minimal="eight"):
+    """--points: the matches triangulated under the pose of the refined chain (consensus = M > 0: of the consensus chain).  Prints one
+    line -- the robust reprojection cost, the share in front of both cameras, the mean parallax in degrees -- and writes the rows that are
+    in front of both cameras with a Cauchy weight w / (1 + reproj / tau^2) of at least 0.5: an ASCII PLY (x y z in the frame of camera 1,
+    units of the baseline; red green blue from image 1 at the match's pixel), or with a .npz suffix the arrays of every row (points,
+    depth1, depth2, reproj, parallax, weight, keep, stat, pose)."""
+    H, W = images.shape[-2:]
+    sy, sx = H / orig_hw[0], W / orig_hw[1]
+    K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
+    kw = dict(hypotheses=consensus, seed=seed, minimal=minimal) if consensus else {}
+    ms = model.structure_from_matches(images, K, chain="consensus" if consensus else "refined", refine=refine, subtoken=subtoken, **kw)
+    st = ms.structure
+    print("structure: reprojection cost %.6e, in front of both cameras %.4f, mean parallax %.3f deg"
+          % (float(st.stat[0, 0]), float(st.stat[0, 1]), np.degrees(float(st.stat[0, 2]))))
+    weight = ms.weights[0].clamp(min=0).nan_to_num(0.0) / (1 + st.reproj[0] / ms.tau[0] ** 2)
+    keep = (st.depth1[0] > 0) & (st.depth2[0] > 0) & (weight >= 0.5)
+    if path.endswith(".npz"):
+        np.savez(path, points=st.points[0].cpu().numpy(), depth1=st.depth1[0].cpu().numpy(), depth2=st.depth2[0].cpu().numpy(),
+                 reproj=st.reproj[0].cpu().numpy(), parallax=st.parallax[0].cpu().numpy(), weight=weight.cpu().numpy(),
+                 keep=keep.cpu().numpy(), stat=st.stat[0].cpu().numpy(), pose=ms.pose[0].cpu().numpy())
+        return
+    px = (ms.x1[0] * K[0, 0, :2] + K[0, 0, 2:]).round().long()                       # the match's pixel in image 1
+    u, v = px[:, 0].clamp(0, W - 1), px[:, 1].clamp(0, H - 1)
+    rgb = images[0, 0][:, v, u].t().flip(1).clamp(0, 255).round().long()             # the images are BGR
+    pts, rgb = st.points[0][keep].cpu().tolist(), rgb[keep].cpu().tolist()
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\ncomment camera 1 frame, units of the baseline\nelement vertex %d\n" % len(pts))
+        f.write("property float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+        for p_, c in zip(pts, rgb):
+            f.write("%.6f %.6f %.6f %d %d %d\n" % (p_[0], p_[1], p_[2], c[0], c[1], c[2]))
 
 
 def write_matches(model, images, path, subtoken=None):

@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so and librelpose_homography.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so and librelpose_triangulate.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -36,6 +36,10 @@ FIVEPOINT_SOURCES = ["five_point.hip"]
 HOMOGRAPHY_CSRC = os.path.join(HERE, "csrc_homography")
 HOMOGRAPHY_LIB = os.path.join(HERE, "librelpose_homography.so")
 HOMOGRAPHY_SOURCES = ["homography.hip"]
+# the triangulation library (include/relpose_triangulate.h): a ninth library, the same pattern
+TRIANGULATE_CSRC = os.path.join(HERE, "csrc_triangulate")
+TRIANGULATE_LIB = os.path.join(HERE, "librelpose_triangulate.so")
+TRIANGULATE_SOURCES = ["triangulate.hip"]
 ARCH = "gfx950"
 
 
@@ -85,10 +89,14 @@ def homography_needs_build():
     return _stale(HOMOGRAPHY_LIB, HOMOGRAPHY_CSRC, HOMOGRAPHY_SOURCES, _homography_headers())
 
 
+def triangulate_needs_build():
+    return _stale(TRIANGULATE_LIB, TRIANGULATE_CSRC, TRIANGULATE_SOURCES, _triangulate_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All eight libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All nine libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -109,6 +117,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, FIVEPOINT_LIB, FIVEPOINT_CSRC, FIVEPOINT_SOURCES, _fivepoint_headers())
             if force or homography_needs_build():
                 _build_locked(verbose, force, HOMOGRAPHY_LIB, HOMOGRAPHY_CSRC, HOMOGRAPHY_SOURCES, _homography_headers())
+            if force or triangulate_needs_build():
+                _build_locked(verbose, force, TRIANGULATE_LIB, TRIANGULATE_CSRC, TRIANGULATE_SOURCES, _triangulate_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -145,6 +155,10 @@ def _fivepoint_headers():
 
 def _homography_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_homography.h")]
+
+
+def _triangulate_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_triangulate.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

@@ -172,6 +172,16 @@ HOMOGRAPHY_MAX_P, HOMOGRAPHY_MAX_M, HOMOGRAPHY_MAX_ITERS = (_HOMOGRAPHY_CONSTS[k
 HOMOGRAPHY_EXPORTS = tuple(_HOMOGRAPHY_PROTOTYPES)
 
 
+# the triangulation library (include/relpose_triangulate.h -> librelpose_triangulate.so): the same parser, errcheck and RP_E* codes a ninth time
+_TRIANGULATE_LIB = None
+TRIANGULATE_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_triangulate.h")
+with open(TRIANGULATE_HEADER) as _f:
+    _TRIANGULATE_CONSTS, _, _TRIANGULATE_PROTOTYPES, _TRIANGULATE_STATUS = _header_contract(_f.read(), "relpose_triangulate.h")
+TRIANGULATE_ABI_VERSION = _TRIANGULATE_CONSTS["RP_TRIANGULATE_ABI_VERSION"]
+TRIANGULATE_MAX_P = _TRIANGULATE_CONSTS["RP_TRIANGULATE_MAX_P"]
+TRIANGULATE_EXPORTS = tuple(_TRIANGULATE_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -387,6 +397,32 @@ def load_homography():
         if name in _HOMOGRAPHY_STATUS:
             fn.errcheck = _raise_on_status
     _HOMOGRAPHY_LIB = lib
+    return lib
+
+
+def load_triangulate():
+    """Load (building if absent or stale) and type librelpose_triangulate.so.  Raises on any failure: there is no fallback."""
+    global _TRIANGULATE_LIB
+    if _TRIANGULATE_LIB is not None:
+        return _TRIANGULATE_LIB
+    path = _build.TRIANGULATE_LIB
+    if _build.triangulate_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_triangulate_abi_version.restype = c_int
+    if lib.rp_triangulate_abi_version() != TRIANGULATE_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_triangulate_abi_version(), TRIANGULATE_ABI_VERSION))
+    for name, (res, args) in _TRIANGULATE_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _TRIANGULATE_STATUS:
+            fn.errcheck = _raise_on_status
+    _TRIANGULATE_LIB = lib
     return lib
 
 

@@ -204,6 +204,15 @@ class ViTEss(nn.Module):
         return homography.planar_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, refine, tau, subtoken, radius, vis_min,
                                                    prior)
 
+    def structure_from_matches(self, images, intrinsics, pose=None, chain="refined", **chain_kwargs):
+        """Where the POINTS are: the matches triangulated under a pose -> triangulate.MatchStructure, whose `structure` holds per match the
+        point (frame of camera 1, units of the baseline), its depth in both cameras, the squared reprojection error and the parallax, and
+        per pair the robust reprojection cost, the share in front of both cameras and the mean parallax.  The pose is that of the chain
+        `chain` -- "eight" (pose_from_matches), "refined", "consensus" or "planar" (its first pick), run with `chain_kwargs` -- or the given
+        `pose` [B,7] as it is, e.g. the regressed one.  eval() mode only; changes no module state and does not write to `intrinsics`."""
+        from . import triangulate
+        return triangulate.structure_from_matches(self, images, intrinsics, pose, chain, **chain_kwargs)
+
     def forward(self, images, Gs, intrinsics=None, inference=False):
         if not hasattr(Gs, "data") or isinstance(Gs, np.ndarray):
             Gs = SE3(torch.from_numpy(np.asarray(Gs)).unsqueeze(0).to(images.device).float())
