@@ -57,7 +57,8 @@ const char* rp_target_arch(void);
  * a_layout: 0 = A stored [M,K] (K contiguous), 1 = A stored [K,M] (M contiguous)
  * b_layout: 0 = B stored [N,K] (K contiguous; nn.Linear weight), 1 = B stored [K,N]
  * contiguous extents and all ld* must be multiples of 4 (K only when an operand is K-contiguous).
- * batch > 1: independent problems at A + i*stride_a etc. (split_k must be 1).
+ * batch > 1: independent problems at A + i*stride_a etc. (split_k must be 1); stride_a / stride_b / stride_c must be
+ *   multiples of 4 elements like the ld* (RP_EALIGN otherwise): every problem starts on a 16-byte boundary.
  * split_k > 1: partial products go to `workspace` ([split_k][M][N] floats) and are reduced in a
  *   fixed order by a second kernel that also applies the epilogue (deterministic).
  * epilogue, in this order:  v += bias[n];  pre_out[m][n] = v;  act (0 none, 1 exact-erf GELU,
@@ -116,7 +117,7 @@ typedef struct RpGemm {
   int defer_reduce; /* split_k > 1 with no epilogue operands only: launch the main kernel and leave the partial slabs in `workspace`
                      * (which the caller then keeps alive and private to this call); the caller finishes C later with ONE
                      * rp_splitk_reduce_multi over several such calls -- the four weight-gradient GEMMs of a transformer block end in
-                     * one reduce launch instead of four */
+                     * one reduce launch instead of four.  With an epilogue operand: RP_EUNSUPPORTED, before anything is launched */
 } RpGemm;
 
 /* hipEvent helpers for ev_start / ev_stop (so that a ctypes host needs no second library): create / destroy / elapsed ms */

@@ -412,6 +412,8 @@ extern "C" int rp_gemm(const RpGemm* g, void* stream) {
   const int batch = g->batch > 0 ? g->batch : 1;
   const int split = g->split_k > 0 ? g->split_k : 1;
   if (batch > 1 && split > 1) return RP_EUNSUPPORTED;
+  // problem i starts at base + i * stride: the 16-byte loads, LDS-DMA granules and 16-byte stores need every start aligned
+  if (batch > 1 && ((g->stride_a | g->stride_b | g->stride_c) & 3)) return RP_EALIGN;
   if (split > 1) {
     if (g->N & 3) return RP_EALIGN;
     if (!g->workspace || g->workspace_bytes < rp_gemm_workspace_bytes(g->M, g->N, split)) return RP_EWORKSPACE;
@@ -465,6 +467,8 @@ extern "C" int rp_gemm(const RpGemm* g, void* stream) {
   if (g->colsum_part && (split > 1 || batch > 1 || (g->N & 3) || (g->a_layout == 1 && g->b_layout == 1))) return RP_EUNSUPPORTED;
   if (p.limbs != 0 && p.limbs != 1 && p.limbs != 3) return RP_EUNSUPPORTED;
   if (g->trans_c && (split == 1 || g->bias || g->pre_out || g->aux || g->residual)) return RP_EUNSUPPORTED;
+  // rp_splitk_reduce_multi applies no epilogue: refused here, before anything is launched into the workspace
+  if (split > 1 && g->defer_reduce && (g->bias || g->pre_out || g->act || g->dact || g->aux || g->residual)) return RP_EUNSUPPORTED;
   // tile shape (TM,TN) = wave tile in 32x32 units; measured on MI355X (tools/gemm_tiles.py): with fp32 MFMA (64
   // cycles per 32x32x2) operand reuse is cheap and occupancy wins -- 128x64 / 64x192 tiles beat 128x192.
   int tm = g->M <= 64 ? 1 : 2;
@@ -500,10 +504,7 @@ extern "C" int rp_gemm(const RpGemm* g, void* stream) {
   else launch_layouts<0>(p, nz, g->a_layout, g->b_layout, tm, tn, st);
   if (g->ev_stop) (void)hipEventRecord((hipEvent_t)g->ev_stop, st);
   RP_CHECK_LAUNCH();
-  if (split > 1 && g->defer_reduce) {
-    if (g->bias || g->pre_out || g->act || g->dact || g->aux || g->residual) return RP_EUNSUPPORTED;
-    return RP_OK;                   // the caller finishes C with rp_splitk_reduce_multi
-  }
+  if (split > 1 && g->defer_reduce) return RP_OK;   // the caller finishes C with rp_splitk_reduce_multi
   if (split > 1) {
     GemmP r = p;
     r.C = g->C;
