@@ -1,5 +1,6 @@
-// block_sum.h -- the workgroup reduction of the small solver libraries (csrc_eightpoint/eight_point.hip, csrc_refine/refine_pose.hip):
-// sums over a workgroup of 256 threads, delivered to EVERY thread with the same bits, one barrier per call.
+// block_sum.h -- the workgroup reduction of the six two-view geometry libraries (eight-point, refinement, consensus, five-point,
+// homography, structure; the select kernels of csrc/consensus_core.h reduce through it too): sums over a workgroup of 256 threads,
+// delivered to EVERY thread with the same bits, one barrier per call.
 //
 // Within a wave by xor shuffles (wave_sum), across the four waves through an LDS buffer the caller owns, summed by every thread in the
 // same fixed order ((w0 + w1) + w2) + w3 -- so whatever a kernel derives from the sums (a rotation, a skip decision, a 5 x 5 solve) is

@@ -21,6 +21,7 @@
 #include "../csrc/common.h"
 #include "../csrc/block_sum.h"
 #include "../csrc/svd3x3.h"
+#include "../csrc/two_view.h"
 #include "../../include/relpose_eightpoint.h"
 
 namespace {
@@ -38,15 +39,6 @@ struct Smem {
   float red[2][NW][RED];
   float V[9][9];               // V[column][row]
 };
-
-// Sampson distance of x1 <-> x2 under e (row-major), as rel_pose_amd/readout.py: sampson_distance; 0 where the denominator is 0
-RP_DEV float sampson(const float (&e)[9], float2 a, float2 b) {
-  const float l2x = e[0] * a.x + e[1] * a.y + e[2], l2y = e[3] * a.x + e[4] * a.y + e[5], l2z = e[6] * a.x + e[7] * a.y + e[8];
-  const float l1x = e[0] * b.x + e[3] * b.y + e[6], l1y = e[1] * b.x + e[4] * b.y + e[7];
-  const float r = b.x * l2x + b.y * l2y + l2z;
-  const float den = l2x * l2x + l2y * l2y + l1x * l1x + l1y * l1y;
-  return den > 0.f ? r * r / den : 0.f;
-}
 
 __global__ __launch_bounds__(NT) void eight_point_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
                                                           const float* __restrict__ w, const float* __restrict__ tau, float* E,

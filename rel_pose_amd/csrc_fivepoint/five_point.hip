@@ -1,26 +1,27 @@
-// five_point.hip -- rp_five_point_consensus: the consensus of csrc_consensus/consensus.hip with the calibrated five-point solver as its
-// minimal solver (librelpose_fivepoint.so).
+// five_point.hip -- rp_five_point_consensus: the consensus of csrc/consensus_core.h with the calibrated five-point solver as its minimal
+// solver (librelpose_fivepoint.so).
 //
 // Two launches; include/relpose_fivepoint.h states the sampler, the solve, the slots, the score and the selection.
 //   hypothesis_kernel   grid n * ceil(M / 256) (problem-major, one dimension), 256 threads.
-//     stage    as in consensus.hip: flags to LDS, the ordered prefix sum over contiguous runs, the rows of positive weight COMPACTED
-//              into LDS (42 496 B).  Four barriers; from there on no thread talks to another.
-//     solve    one lane, one sample, fp64: Floyd's five draws, five Householder reflections of the 9 x 5 transpose, the null-space basis
-//              X, Y, Z, W, the ten cubics by products of linear and quadratic forms (every index static), Gauss-Jordan with row
-//              pivoting on the lane's private 10 x 20 array (runtime row indices: it lives in scratch, 1600 B per lane), Nister's
+//     stage    the core: the rows of positive weight COMPACTED into LDS (42 496 B).  Four barriers; from there on no thread talks to
+//              another.
+//     solve    one lane, one sample, fp64: Floyd's five draws (the core), five Householder reflections of the 9 x 5 transpose, the
+//              null-space basis X, Y, Z, W, the ten cubics by products of linear and quadratic forms (every index static), Gauss-Jordan
+//              with row pivoting on the lane's private 10 x 20 array (runtime row indices: it lives in scratch, 1600 B per lane), Nister's
 //              tenth-degree polynomial p = det B(z), its real roots by bracketing through the derivatives of p.  Every loop has a
 //              fixed trip count: 48 halvings and 4 guarded Newton steps per bracket, at most d brackets at degree d.
-//     score    fp32: each root is rounded at norm 1, projected with svd3x3_dev, signed, and walks the K compacted rows exactly as
-//              consensus.hip does (every lane reads the SAME LDS address: a broadcast); valid roots fill the sample's slots in
-//              ascending z, the remaining slots are written as invalid.
-//   select_kernel       grid n, 256 threads: the lowest-index argmin of hyp_cost over the 10 M slots, the Sampson distances at the winner,
-//              w_out, and the sums of stat by block_sum.
+//     score    fp32: each root is rounded at norm 1, projected with svd3x3_dev, signed, and walks the K compacted rows through the core's
+//              cost loop (every lane reads the SAME LDS address: a broadcast); valid roots fill the sample's slots in ascending z, the
+//              remaining slots are written as invalid.
+//   select_kernel       grid n, 256 threads: the core's lowest-index argmin of hyp_cost over the 10 M slots, the Sampson distances at the
+//              winner and w_out; the sums of stat by block_sum.
 // No atomics, no workspace; the only output that is read is hyp_cost / hyp_E, by the second launch after the first wrote all of it.
-// mix and sampson restate the arithmetic that relpose_consensus.h spells out; consensus.hip is not touched.
 #include <float.h>
 #include "../csrc/common.h"
 #include "../csrc/block_sum.h"
 #include "../csrc/svd3x3.h"
+#include "../csrc/two_view.h"
+#include "../csrc/consensus_core.h"
 #include "../../include/relpose_fivepoint.h"
 
 namespace {
@@ -28,35 +29,10 @@ namespace {
 constexpr int NT = BLOCK_SUM_THREADS;                // threads per workgroup
 constexpr int NW = BLOCK_SUM_WAVES;
 constexpr int MAXP = RP_FIVEPOINT_MAX_P;
-constexpr int ROWS = (MAXP + NT - 1) / NT;           // rows one thread stages: 7
 constexpr int RED = 4;                               // floats per wave in the reduction buffer of select_kernel
 constexpr int NR = RP_FIVEPOINT_ROOTS;
 constexpr double MIN_PIVOT = 1e-12;                  // a Householder column norm or an elimination pivot below this: breakdown
 constexpr int HALVINGS = 48, NEWTON = 4;             // per bracket
-constexpr float FINITE = 3.0e38f;                    // |v| <= FINITE: v is a number
-
-struct Rows {
-  float2 a[MAXP], b[MAXP];     // the rows of positive weight, ascending: x1, x2
-  float w[MAXP];
-  int pos[MAXP];               // their row numbers
-  int cnt[NT];
-};                             // 42 496 B
-
-RP_DEV uint32_t mix(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
-// Sampson distance of x1 <-> x2 under e (row-major), as csrc_eightpoint/eight_point.hip; 0 where the denominator is 0
-RP_DEV float sampson(const float (&e)[9], float2 a, float2 b) {
-  const float l2x = e[0] * a.x + e[1] * a.y + e[2], l2y = e[3] * a.x + e[4] * a.y + e[5], l2z = e[6] * a.x + e[7] * a.y + e[8];
-  const float l1x = e[0] * b.x + e[3] * b.y + e[6], l1y = e[1] * b.x + e[4] * b.y + e[7];
-  const float r = b.x * l2x + b.y * l2y + l2z;
-  const float den = l2x * l2x + l2y * l2y + l1x * l1x + l1y * l1y;
-  return den > 0.f ? r * r / den : 0.f;
-}
 
 // ---- polynomials in (x, y, z).  linear: x y z 1;  quadratic: x^2 y^2 z^2 xy xz yz x y z 1;  cubic: the 20 columns of the header
 // q += s a b
@@ -328,67 +304,15 @@ RP_DEV int five_point(const float2 (&p1)[5], const float2 (&p2)[5], double (&N)[
 __global__ __launch_bounds__(NT) void hypothesis_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
                                                          const float* __restrict__ w, const float* __restrict__ tau, uint32_t seed,
                                                          float* hyp_E, float* hyp_cost, int* samples, int P, int M, int chunks) {
-  __shared__ Rows sm;
-  const int tid = threadIdx.x;
+  __shared__ ConsensusRows<MAXP> sm;
   const long long b = blockIdx.x / chunks;
-  const int m = (blockIdx.x % chunks) * NT + tid;
+  const int m = (blockIdx.x % chunks) * NT + threadIdx.x;
   const float2* X1 = reinterpret_cast<const float2*>(x1) + b * P;
   const float2* X2 = reinterpret_cast<const float2*>(x2) + b * P;
-  const float* W = w ? w + b * P : nullptr;
-  // ---- stage: the flags of the rows (coalesced), the ordered prefix over contiguous runs of them, then the rows of positive weight
-  for (int r = tid; r < P; r += NT) sm.pos[r] = (W ? fmaxf(W[r], 0.f) : 1.f) > 0.f ? 1 : 0;
-  __syncthreads();
-  const int per = (P + NT - 1) / NT;                // thread t numbers the rows t * per .. t * per + per - 1
-  int flag[ROWS], mine = 0;
-#pragma unroll
-  for (int i = 0; i < ROWS; ++i) {
-    const int r = tid * per + i;
-    flag[i] = i < per && r < P ? sm.pos[r] : 0;     // (into registers: pos is overwritten below)
-    mine += flag[i];
-  }
-  sm.cnt[tid] = mine;
-  __syncthreads();
-  int at = 0, K = 0;
-  for (int t = 0; t < NT; ++t) {
-    const int c = sm.cnt[t];
-    K += c;
-    at += t < tid ? c : 0;
-  }
-#pragma unroll
-  for (int i = 0; i < ROWS; ++i) {
-    if (flag[i]) sm.pos[at++] = tid * per + i;      // (every flag was read before the barrier above)
-  }
-  __syncthreads();
-  for (int j = tid; j < K; j += NT) {               // ascending rows: close to coalesced
-    const int r = sm.pos[j];
-    sm.a[j] = X1[r];
-    sm.b[j] = X2[r];
-    sm.w[j] = W ? W[r] : 1.f;
-  }
-  __syncthreads();
+  const int K = consensus_stage(sm, X1, X2, w ? w + b * P : nullptr, P);
   if (m >= M) return;                               // (behind the last barrier)
-  // ---- sample
   uint32_t c[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) c[k] = 0u;
-  if (K >= 5) {
-    const uint32_t s = mix(mix(seed + 0x9E3779B9u * (uint32_t)(b + 1)) ^ (uint32_t)m);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const uint32_t r = mix(s + 0x9E3779B9u * (uint32_t)(k + 1));
-      const uint32_t j = (uint32_t)(K - 5 + k);
-      const uint32_t t = (uint32_t)(((uint64_t)r * (uint64_t)(j + 1u)) >> 32);
-      bool seen = false;
-#pragma unroll
-      for (int l = 0; l < k; ++l) seen = seen || c[l] == t;
-      c[k] = seen ? j : t;
-    }
-  }
-  if (samples) {
-    int* S = samples + (b * M + m) * 5;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) S[k] = K >= 5 ? sm.pos[c[k]] : 0;
-  }
+  consensus_sample(sm, seed, b, m, M, K, samples, c);
   // ---- solve
   const float ta = tau[b], tau2 = ta * ta;
   double N[4][9], xs[NR], ys[NR], zs[NR];
@@ -421,7 +345,7 @@ __global__ __launch_bounds__(NT) void hypothesis_kernel(const float* __restrict_
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       F[t] = (float)(ed[t] * inv);
-      ok = ok && fabsf(F[t]) <= FINITE;
+      ok = ok && fabsf(F[t]) <= RP_FINITE;
     }
     if (!ok) continue;
     float u[3][3], sv[3], v[3][3], e[9];
@@ -430,26 +354,9 @@ __global__ __launch_bounds__(NT) void hypothesis_kernel(const float* __restrict_
     for (int r = 0; r < 3; ++r)
 #pragma unroll
       for (int cc = 0; cc < 3; ++cc) e[3 * r + cc] = u[0][r] * v[0][cc] + u[1][r] * v[1][cc];
-    float big = fabsf(e[0]), lead = e[0];
-    ok = fabsf(e[0]) <= FINITE;
-#pragma unroll
-    for (int t = 1; t < 9; ++t) {
-      ok = ok && fabsf(e[t]) <= FINITE;
-      if (fabsf(e[t]) > big) { big = fabsf(e[t]); lead = e[t]; }
-    }
-    if (!ok) continue;
-    if (lead < 0.f) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t) e[t] = -e[t];
-    }
-    float acc = 0.f, wsum = 0.f;
-    for (int j = 0; j < K; ++j) {
-      const float wt = sm.w[j];
-      const float d = sampson(e, sm.a[j], sm.b[j]);
-      acc += wt * (tau2 * log1pf(d / tau2));
-      wsum += wt;
-    }
-    const float cost = acc / wsum;
+    if (!all_finite(e)) continue;
+    sign_rule(e);
+    const float cost = consensus_cost(sm, e, K, tau2, SampsonDistance());
     if (!(cost < FLT_MAX)) continue;                  // (a NaN, too)
 #pragma unroll
     for (int t = 0; t < 9; ++t) HE[slot * 9 + t] = e[t];
@@ -471,51 +378,16 @@ __global__ __launch_bounds__(NT) void select_kernel(const float* __restrict__ x1
   __shared__ float red[2][NW][RED];
   __shared__ float bc[NT];
   __shared__ int bi[NT];
-  const int tid = threadIdx.x;
   const long long b = blockIdx.x;
   const int S = M * NR;                                // slots of this problem: at most 40 960
-  const float2* X1 = reinterpret_cast<const float2*>(x1) + b * P;
-  const float2* X2 = reinterpret_cast<const float2*>(x2) + b * P;
-  const float* W = w ? w + b * P : nullptr;
-  float* WO = w_out ? w_out + b * P : nullptr;
   const float* HC = hyp_cost + b * S;
-  // ---- the lowest-index minimum among the valid slots, and their number
-  float lo = FLT_MAX, nvalid = 0.f;
-  int arg = -1;
-  for (int s = tid; s < S; s += NT) {
-    const float c = HC[s];
-    nvalid += c < FLT_MAX ? 1.f : 0.f;
-    if (c < lo) { lo = c; arg = s; }                 // (ascending s: the first of equal costs stays)
-  }
-  bc[tid] = lo;
-  bi[tid] = arg;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      const float c = bc[tid + s];
-      const int i = bi[tid + s];
-      if (i >= 0 && (c < bc[tid] || bi[tid] < 0 || (c == bc[tid] && i < bi[tid]))) { bc[tid] = c; bi[tid] = i; }
-    }
-    __syncthreads();
-  }
-  const int win = bi[0];
-  float e[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) e[i] = win >= 0 ? hyp_E[(b * S + win) * 9 + i] : 0.f;
-  const float ta = tau[b], tau2 = win >= 0 ? ta * ta : 1.f;
-  // ---- the weights at the winner; sum of the weights, of those within tau, count of the positive ones, count of the valid slots
-  float s4[4] = {0.f, 0.f, 0.f, nvalid};
-  for (int r = tid; r < P; r += NT) {
-    const float wt = W ? fmaxf(W[r], 0.f) : 1.f;
-    const float d = sampson(e, X1[r], X2[r]);
-    s4[0] += wt;
-    s4[1] += d <= tau2 ? wt : 0.f;
-    s4[2] += wt > 0.f ? 1.f : 0.f;
-    if (WO) WO[r] = win >= 0 ? wt / (1.f + d / tau2) : wt;
-  }
+  float e[9], s4[4];
+  const int win = consensus_select(bc, bi, reinterpret_cast<const float2*>(x1) + b * P, reinterpret_cast<const float2*>(x2) + b * P,
+                                   w ? w + b * P : nullptr, w_out ? w_out + b * P : nullptr, HC, hyp_E + b * S * 9, S, P, tau[b],
+                                   SampsonDistance(), e, s4);
   int phase = 0;
   block_sum(s4, red, phase);
-  if (tid == 0) {
+  if (threadIdx.x == 0) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) E[b * 9 + i] = e[i];
     best[b * 2] = win >= 0 ? win / NR : -1;
@@ -534,18 +406,6 @@ extern "C" int rp_fivepoint_abi_version(void) { return RP_FIVEPOINT_ABI_VERSION;
 extern "C" int rp_five_point_consensus(const float* x1, const float* x2, const float* w, const float* tau, int seed, float* E, int* best,
                                        float* stat, float* w_out, float* hyp_E, float* hyp_cost, int* samples, int P, int M, int n,
                                        void* stream) {
-  if (n <= 0 || P < 5 || M < 1 || !x1 || !x2 || !tau || !E || !best || !stat || !hyp_E || !hyp_cost) return RP_EBADSHAPE;
-  if (P > RP_FIVEPOINT_MAX_P || M > RP_FIVEPOINT_MAX_M) return RP_EUNSUPPORTED;
-  const int chunks = (M + NT - 1) / NT;
-  if ((long long)n * chunks > 2147483647LL) return RP_EUNSUPPORTED;
-  if (((uintptr_t)x1 | (uintptr_t)x2) & 7) return RP_EALIGN;
-  if (((uintptr_t)w | (uintptr_t)tau | (uintptr_t)E | (uintptr_t)best | (uintptr_t)stat | (uintptr_t)w_out | (uintptr_t)hyp_E |
-       (uintptr_t)hyp_cost | (uintptr_t)samples) & 3)
-    return RP_EALIGN;
-  hipLaunchKernelGGL(hypothesis_kernel, dim3(n * chunks), dim3(NT), 0, (hipStream_t)stream, x1, x2, w, tau, (uint32_t)seed, hyp_E, hyp_cost,
-                     samples, P, M, chunks);
-  RP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(select_kernel, dim3(n), dim3(NT), 0, (hipStream_t)stream, x1, x2, w, tau, hyp_E, hyp_cost, E, best, stat, w_out, P, M);
-  RP_CHECK_LAUNCH();
-  return RP_OK;
+  return consensus_launch<5, RP_FIVEPOINT_MAX_P, RP_FIVEPOINT_MAX_M, hypothesis_kernel, select_kernel>(
+      x1, x2, w, tau, seed, E, best, stat, w_out, hyp_E, hyp_cost, samples, P, M, n, stream);
 }

@@ -1,15 +1,16 @@
 // homography.hip -- the plane-induced homography behind the matches (librelpose_homography.so): rp_homography_consensus,
 // rp_homography_refine, rp_pose_from_homography.  include/relpose_homography.h states all arithmetic.
 //
-//   hypothesis_kernel   grid n * ceil(M / 256) (problem-major), 256 threads: the staging of csrc_consensus/consensus.hip (flags, ordered
-//              prefix, compacted rows in LDS; four barriers), then one lane per hypothesis: Floyd's four draws, Hartley normalisation, the
-//              8 x 9 DLT matrix in registers, eight Householder reflections of its transpose (every loop unrolled, every index static: no
-//              scratch), the null vector, H = T2^-1 H^ T1, Frobenius norm 1, the sign rule; the lane then walks the K compacted rows
-//              (LDS broadcast reads) and sums the robust transfer cost in a fixed order.
-//   select_kernel       grid n, 256 threads: the lowest-index argmin of hyp_cost (a tree in LDS), w_out and stat at the winner.
+//   hypothesis_kernel   grid n * ceil(M / 256) (problem-major), 256 threads: the staging of csrc/consensus_core.h (flags, ordered
+//              prefix, compacted rows in LDS; four barriers), then one lane per hypothesis: Floyd's four draws (the core), Hartley
+//              normalisation, the 8 x 9 DLT matrix in registers, its null vector by eight Householder reflections of the transpose
+//              (csrc/two_view.h: every loop unrolled, every index static: no scratch), H = T2^-1 H^ T1, Frobenius norm 1, the sign rule;
+//              the lane then walks the K compacted rows (the core's cost loop, LDS broadcast reads) and sums the robust transfer cost in
+//              a fixed order.
+//   select_kernel       grid n, 256 threads: the core's lowest-index argmin of hyp_cost (a tree in LDS), w_out and stat at the winner.
 //   refine_kernel       grid n, 256 threads: Levenberg-Marquardt over the eight generators of sl(3).  A thread's rows (at most 7) stay in
 //              registers; per iteration ONE fused 44-value reduction (36 of the normal matrix, 8 of the gradient), the 8 x 8 Cholesky
-//              and the retraction redundantly in every thread, one one-value reduction for the trial cost: two barriers.
+//              (csrc/two_view.h) and the retraction redundantly in every thread, one one-value reduction for the trial cost: two barriers.
 //   decompose_kernel    grid n, 256 threads: every thread decomposes H redundantly (svd3x3_dev, closed form); one reduction fixes the sign
 //              of H, one fused eight-value reduction gives visibility and Sampson cost of the four candidates.
 // No atomics, no workspace; the only output that is read is hyp_cost / hyp_H, by select_kernel after hypothesis_kernel wrote all of it.
@@ -17,6 +18,8 @@
 #include "../csrc/common.h"
 #include "../csrc/block_sum.h"
 #include "../csrc/svd3x3.h"
+#include "../csrc/two_view.h"
+#include "../csrc/consensus_core.h"
 #include "../../include/relpose_homography.h"
 
 namespace {
@@ -29,26 +32,10 @@ constexpr int RED = 4;                               // floats per wave in the r
 constexpr int NPAR = 8;                              // degrees of freedom of H
 constexpr int LMRED = NPAR * (NPAR + 1) / 2 + NPAR;  // 44: the upper triangle of the normal matrix and the gradient
 constexpr int DRED = 8;                              // decompose_kernel: (visibility, Sampson cost) of four candidates
-constexpr float MIN_SCALE = 1e-30f;                  // a mean distance or a Frobenius norm below this counts as 0
-constexpr float FINITE = 3.0e38f;                    // |v| <= FINITE: v is a number
 constexpr float DEN_MIN = 1e-30f, D_MAX = 1e30f;     // the clamps of the transfer distance
 constexpr float LAMBDA0 = 1e-3f, LAMBDA_MIN = 1e-7f, LAMBDA_MAX = 1e7f;
 constexpr float ROTATION_GAP = 1e-4f;                // sigma_1 - sigma_3 below this: pure rotation
 constexpr float RANK_MIN = 1e-6f;                    // s_2 <= RANK_MIN s_1: H has no middle singular value to scale by
-
-struct Rows {
-  float2 a[MAXP], b[MAXP];     // the rows of positive weight, ascending: x1, x2
-  float w[MAXP];
-  int pos[MAXP];               // their row numbers
-  int cnt[NT];
-};                             // 42 496 B
-
-RP_DEV uint32_t mix(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
 
 // squared one-sided transfer distance |pi(H x1h) - x2|^2, the denominator clamped below and the value above: independent of the sign of h
 RP_DEV float transfer(const float (&h)[9], float2 a, float2 b) {
@@ -57,68 +44,30 @@ RP_DEV float transfer(const float (&h)[9], float2 a, float2 b) {
   return fminf((ex * ex + ey * ey) / fmaxf(m2 * m2, DEN_MIN), D_MAX);
 }
 
-// Sampson distance of x1 <-> x2 under e (row-major), as csrc_consensus/consensus.hip; 0 where the denominator is 0
-RP_DEV float sampson(const float (&e)[9], float2 a, float2 b) {
-  const float l2x = e[0] * a.x + e[1] * a.y + e[2], l2y = e[3] * a.x + e[4] * a.y + e[5], l2z = e[6] * a.x + e[7] * a.y + e[8];
-  const float l1x = e[0] * b.x + e[3] * b.y + e[6], l1y = e[1] * b.x + e[4] * b.y + e[7];
-  const float r = b.x * l2x + b.y * l2y + l2z;
-  const float den = l2x * l2x + l2y * l2y + l1x * l1x + l1y * l1y;
-  return den > 0.f ? r * r / den : 0.f;
-}
+// the distance of this library
+struct TransferDistance {
+  RP_DEV float operator()(const float (&h)[9], float2 a, float2 b) const { return transfer(h, a, b); }
+};
 
-// h / |h|_F; false if the norm is below MIN_SCALE or not a number (h is then left as it is)
+// h / |h|_F; false if the norm is below RP_MIN_SCALE or not a number (h is then left as it is)
 RP_DEV bool frob_unit(float (&h)[9]) {
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < 9; ++i) ss += h[i] * h[i];
   const float nrm = sqrtf(ss);
-  if (!(nrm >= MIN_SCALE) || !(nrm <= FINITE)) return false;
+  if (!(nrm >= RP_MIN_SCALE) || !(nrm <= RP_FINITE)) return false;
 #pragma unroll
   for (int i = 0; i < 9; ++i) h[i] = h[i] / nrm;
-  return true;
-}
-
-// the sign rule of rp_eight_point: the entry of largest magnitude, the first of equal ones, is positive
-RP_DEV void sign_rule(float (&h)[9]) {
-  float big = fabsf(h[0]), lead = h[0];
-#pragma unroll
-  for (int i = 1; i < 9; ++i) {
-    if (fabsf(h[i]) > big) { big = fabsf(h[i]); lead = h[i]; }
-  }
-  if (lead < 0.f) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) h[i] = -h[i];
-  }
-}
-
-// Hartley transform of four points with unit weights about the pivot p[0]: centroid (cx, cy), scale s; false on a breakdown
-RP_DEV bool normalise4(const float2 (&p)[4], float& cx, float& cy, float& s) {
-  float sx = 0.f, sy = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    sx += p[k].x - p[0].x;
-    sy += p[k].y - p[0].y;
-  }
-  cx = p[0].x + sx / 4.f;
-  cy = p[0].y + sy / 4.f;
-  float m = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float dx = p[k].x - cx, dy = p[k].y - cy;
-    m += sqrtf(dx * dx + dy * dy);
-  }
-  m = m / 4.f;
-  if (!(m >= MIN_SCALE)) return false;
-  s = sqrtf(2.f) / m;
   return true;
 }
 
 // the four-point DLT on four rows; false: INVALID
 RP_DEV bool minimal_solve(const float2 (&p1)[4], const float2 (&p2)[4], float (&h)[9]) {
   float c1x, c1y, s1, c2x, c2y, s2;
-  if (!normalise4(p1, c1x, c1y, s1) || !normalise4(p2, c2x, c2y, s2)) return false;
+  if (!normalise(p1, c1x, c1y, s1) || !normalise(p2, c2x, c2y, s2)) return false;
   // A[j] = row j of the 8 x 9 matrix: the j-th COLUMN of the 9 x 8 transpose
-  float A[8][9];
+  Mat8x9 m;
+  float (&A)[8][9] = m.a;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float ax = (p1[k].x - c1x) * s1, ay = (p1[k].y - c1y) * s1, bx = (p2[k].x - c2x) * s2, by = (p2[k].y - c2y) * s2;
@@ -129,41 +78,8 @@ RP_DEV bool minimal_solve(const float2 (&p1)[4], const float2 (&p2)[4], float (&
     A[2 * k + 1][3] = ax;  A[2 * k + 1][4] = ay;  A[2 * k + 1][5] = 1.f;
     A[2 * k + 1][6] = -by * ax; A[2 * k + 1][7] = -by * ay; A[2 * k + 1][8] = -by;
   }
-  // Householder QR of the transpose, column by column: H_j = I - beta_j v_j v_j^T zeroes column j below its diagonal; v_j stays in
-  // A[j][j ..].  A zero column gets beta = 0, v = 0: no reflection.
-  float beta[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float sig = 0.f;
-#pragma unroll
-    for (int i = j; i < 9; ++i) sig += A[j][i] * A[j][i];
-    const float nrm = sqrtf(sig);
-    const float den = sig + fabsf(A[j][j]) * nrm;
-    beta[j] = den > 0.f ? 1.f / den : 0.f;
-    A[j][j] += copysignf(nrm, A[j][j]);
-#pragma unroll
-    for (int k = j + 1; k < 8; ++k) {
-      float t = 0.f;
-#pragma unroll
-      for (int i = j; i < 9; ++i) t += A[j][i] * A[k][i];
-      t *= beta[j];
-#pragma unroll
-      for (int i = j; i < 9; ++i) A[k][i] -= t * A[j][i];
-    }
-  }
-  // the null vector: the last column of Q = H_0 .. H_7
   float f[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) f[i] = i == 8 ? 1.f : 0.f;
-#pragma unroll
-  for (int j = 7; j >= 0; --j) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = j; i < 9; ++i) t += A[j][i] * f[i];
-    t *= beta[j];
-#pragma unroll
-    for (int i = j; i < 9; ++i) f[i] -= t * A[j][i];
-  }
+  null_vector_8x9(m, f);
   // H = T2^-1 H^ T1, T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]], T^-1 = [[1/s, 0, cx], [0, 1/s, cy], [0, 0, 1]]
   float G[9];
 #pragma unroll
@@ -178,10 +94,7 @@ RP_DEV bool minimal_solve(const float2 (&p1)[4], const float2 (&p2)[4], float (&
     h[3 + j] = G[3 + j] / s2 + c2y * G[6 + j];
     h[6 + j] = G[6 + j];
   }
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) ok = ok && fabsf(h[i]) <= FINITE;
-  if (!ok || !frob_unit(h)) return false;
+  if (!all_finite(h) || !frob_unit(h)) return false;
   sign_rule(h);
   return true;
 }
@@ -189,67 +102,15 @@ RP_DEV bool minimal_solve(const float2 (&p1)[4], const float2 (&p2)[4], float (&
 __global__ __launch_bounds__(NT) void hypothesis_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
                                                          const float* __restrict__ w, const float* __restrict__ tau, uint32_t seed,
                                                          float* hyp_H, float* hyp_cost, int* samples, int P, int M, int chunks) {
-  __shared__ Rows sm;
-  const int tid = threadIdx.x;
+  __shared__ ConsensusRows<MAXP> sm;
   const long long b = blockIdx.x / chunks;
-  const int m = (blockIdx.x % chunks) * NT + tid;
+  const int m = (blockIdx.x % chunks) * NT + threadIdx.x;
   const float2* X1 = reinterpret_cast<const float2*>(x1) + b * P;
   const float2* X2 = reinterpret_cast<const float2*>(x2) + b * P;
-  const float* W = w ? w + b * P : nullptr;
-  // ---- stage: the flags of the rows (coalesced), the ordered prefix over contiguous runs of them, then the rows of positive weight
-  for (int r = tid; r < P; r += NT) sm.pos[r] = (W ? fmaxf(W[r], 0.f) : 1.f) > 0.f ? 1 : 0;
-  __syncthreads();
-  const int per = (P + NT - 1) / NT;                // thread t numbers the rows t * per .. t * per + per - 1
-  int flag[ROWS], mine = 0;
-#pragma unroll
-  for (int i = 0; i < ROWS; ++i) {
-    const int r = tid * per + i;
-    flag[i] = i < per && r < P ? sm.pos[r] : 0;     // (into registers: pos is overwritten below)
-    mine += flag[i];
-  }
-  sm.cnt[tid] = mine;
-  __syncthreads();
-  int at = 0, K = 0;
-  for (int t = 0; t < NT; ++t) {
-    const int c = sm.cnt[t];
-    K += c;
-    at += t < tid ? c : 0;
-  }
-#pragma unroll
-  for (int i = 0; i < ROWS; ++i) {
-    if (flag[i]) sm.pos[at++] = tid * per + i;      // (every flag was read before the barrier above; at < K <= P)
-  }
-  __syncthreads();
-  for (int j = tid; j < K; j += NT) {               // ascending rows: close to coalesced
-    const int r = sm.pos[j];
-    sm.a[j] = X1[r];
-    sm.b[j] = X2[r];
-    sm.w[j] = W ? W[r] : 1.f;
-  }
-  __syncthreads();
+  const int K = consensus_stage(sm, X1, X2, w ? w + b * P : nullptr, P);
   if (m >= M) return;                               // (behind the last barrier)
-  // ---- sample
   uint32_t c[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) c[k] = 0u;
-  if (K >= 4) {
-    const uint32_t s = mix(mix(seed + 0x9E3779B9u * (uint32_t)(b + 1)) ^ (uint32_t)m);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t r = mix(s + 0x9E3779B9u * (uint32_t)(k + 1));
-      const uint32_t j = (uint32_t)(K - 4 + k);
-      const uint32_t t = (uint32_t)(((uint64_t)r * (uint64_t)(j + 1u)) >> 32);
-      bool seen = false;
-#pragma unroll
-      for (int l = 0; l < k; ++l) seen = seen || c[l] == t;
-      c[k] = seen ? j : t;
-    }
-  }
-  if (samples) {
-    int* S = samples + (b * M + m) * 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) S[k] = K >= 4 ? sm.pos[c[k]] : 0;
-  }
+  consensus_sample(sm, seed, b, m, M, K, samples, c);
   // ---- solve and score
   const float ta = tau[b], tau2 = ta * ta;
   float h[9], cost = FLT_MAX;
@@ -264,14 +125,7 @@ __global__ __launch_bounds__(NT) void hypothesis_kernel(const float* __restrict_
     valid = minimal_solve(p1, p2, h);
   }
   if (valid) {
-    float acc = 0.f, wsum = 0.f;
-    for (int j = 0; j < K; ++j) {
-      const float wt = sm.w[j];
-      const float d = transfer(h, sm.a[j], sm.b[j]);
-      acc += wt * (tau2 * log1pf(d / tau2));
-      wsum += wt;
-    }
-    cost = acc / wsum;
+    cost = consensus_cost(sm, h, K, tau2, TransferDistance());
     valid = cost < FLT_MAX;                         // (false for a NaN, too)
   }
   if (!valid) {
@@ -292,50 +146,15 @@ __global__ __launch_bounds__(NT) void select_kernel(const float* __restrict__ x1
   __shared__ float red[2][NW][RED];
   __shared__ float bc[NT];
   __shared__ int bi[NT];
-  const int tid = threadIdx.x;
   const long long b = blockIdx.x;
-  const float2* X1 = reinterpret_cast<const float2*>(x1) + b * P;
-  const float2* X2 = reinterpret_cast<const float2*>(x2) + b * P;
-  const float* W = w ? w + b * P : nullptr;
-  float* WO = w_out ? w_out + b * P : nullptr;
   const float* HC = hyp_cost + b * M;
-  // ---- the lowest-index minimum among the valid hypotheses, and their number
-  float lo = FLT_MAX, nvalid = 0.f;
-  int arg = -1;
-  for (int m = tid; m < M; m += NT) {
-    const float c = HC[m];
-    nvalid += c < FLT_MAX ? 1.f : 0.f;
-    if (c < lo) { lo = c; arg = m; }               // (ascending m: the first of equal costs stays)
-  }
-  bc[tid] = lo;
-  bi[tid] = arg;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      const float c = bc[tid + s];
-      const int i = bi[tid + s];
-      if (i >= 0 && (c < bc[tid] || bi[tid] < 0 || (c == bc[tid] && i < bi[tid]))) { bc[tid] = c; bi[tid] = i; }
-    }
-    __syncthreads();
-  }
-  const int win = bi[0];
-  float h[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) h[i] = win >= 0 ? hyp_H[(b * M + win) * 9 + i] : 0.f;
-  const float ta = tau[b], tau2 = win >= 0 ? ta * ta : 1.f;
-  // ---- the weights at the winner; sum of the weights, of those within tau, count of the positive ones, count of the valid hypotheses
-  float s4[4] = {0.f, 0.f, 0.f, nvalid};
-  for (int r = tid; r < P; r += NT) {
-    const float wt = W ? fmaxf(W[r], 0.f) : 1.f;
-    const float d = transfer(h, X1[r], X2[r]);
-    s4[0] += wt;
-    s4[1] += d <= tau2 ? wt : 0.f;
-    s4[2] += wt > 0.f ? 1.f : 0.f;
-    if (WO) WO[r] = win >= 0 ? wt / (1.f + d / tau2) : wt;
-  }
+  float h[9], s4[4];
+  const int win = consensus_select(bc, bi, reinterpret_cast<const float2*>(x1) + b * P, reinterpret_cast<const float2*>(x2) + b * P,
+                                   w ? w + b * P : nullptr, w_out ? w_out + b * P : nullptr, HC, hyp_H + b * M * 9, M, P, tau[b],
+                                   TransferDistance(), h, s4);
   int phase = 0;
   block_sum(s4, red, phase);
-  if (tid == 0) {
+  if (threadIdx.x == 0) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) H[b * 9 + i] = h[i];
     best[b] = win;
@@ -344,62 +163,6 @@ __global__ __launch_bounds__(NT) void select_kernel(const float* __restrict__ x1
     stat[b * 4 + 2] = s4[3];
     stat[b * 4 + 3] = s4[2];
   }
-}
-
-// (N + lam diag N) delta = -g in the diagonally scaled form by Cholesky; false on a breakdown.  a: the 36 upper entries of N row by
-// row, then g.
-RP_DEV bool solve8(const float (&a)[LMRED], float lam, float (&delta)[NPAR]) {
-  float N[NPAR][NPAR], sc[NPAR], rhs[NPAR];
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < NPAR; ++i)
-#pragma unroll
-    for (int j = i; j < NPAR; ++j) N[i][j] = N[j][i] = a[k++];
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < NPAR; ++i) {
-    ok = ok && N[i][i] > 0.f && N[i][i] <= FINITE;
-    sc[i] = 1.f / sqrtf(N[i][i]);
-    rhs[i] = a[36 + i] * sc[i];
-  }
-  if (!ok) return false;
-  float L[NPAR][NPAR];
-#pragma unroll
-  for (int j = 0; j < NPAR; ++j) {
-    float p = 1.f + lam;
-#pragma unroll
-    for (int m = 0; m < j; ++m) p = p - L[j][m] * L[j][m];
-    if (!(p > 0.f) || !(p <= FINITE)) return false;
-    L[j][j] = sqrtf(p);
-#pragma unroll
-    for (int i = j + 1; i < NPAR; ++i) {
-      float v = N[i][j] * sc[i] * sc[j];
-#pragma unroll
-      for (int m = 0; m < j; ++m) v = v - L[i][m] * L[j][m];
-      L[i][j] = v / L[j][j];
-    }
-  }
-  float y[NPAR], z[NPAR];
-#pragma unroll
-  for (int i = 0; i < NPAR; ++i) {
-    float v = rhs[i];
-#pragma unroll
-    for (int m = 0; m < i; ++m) v = v - L[i][m] * y[m];
-    y[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = NPAR - 1; i >= 0; --i) {
-    float v = y[i];
-#pragma unroll
-    for (int m = i + 1; m < NPAR; ++m) v = v - L[m][i] * z[m];
-    z[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = 0; i < NPAR; ++i) {
-    delta[i] = -(z[i] * sc[i]);
-    ok = ok && fabsf(delta[i]) <= FINITE;
-  }
-  return ok;
 }
 
 // the robust transfer cost term of one row
@@ -437,7 +200,7 @@ __global__ __launch_bounds__(NT) void refine_kernel(const float* H0, const float
   for (int i = 0; i < 9; ++i) {
     h0[i] = H0[b * 9 + i];
     h[i] = h0[i];
-    degenerate = degenerate || !(fabsf(h0[i]) <= FINITE);
+    degenerate = degenerate || !(fabsf(h0[i]) <= RP_FINITE);
   }
   const float ta = tau[b], tau2 = ta * ta;
   degenerate = degenerate || !frob_unit(h) || !(ta > 0.f);
@@ -502,7 +265,7 @@ __global__ __launch_bounds__(NT) void refine_kernel(const float* H0, const float
     block_sum(a, red, phase);
     // ---- the step and the trial H (uniform): H (I + D), D = sum delta_k G_k
     float delta[NPAR], h1[9];
-    bool solved = solve8(a, lam, delta);
+    bool solved = lm_cholesky_solve(a, lam, delta);
     if (!solved) {
 #pragma unroll
       for (int i = 0; i < NPAR; ++i) delta[i] = 0.f;
@@ -554,48 +317,6 @@ __global__ __launch_bounds__(NT) void refine_kernel(const float* H0, const float
   }
 }
 
-RP_DEV void quat_to_rot(const float (&q)[4], float (&R)[9]) {
-  const float x = q[0], y = q[1], z = q[2], w = q[3];
-  R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - z * w);       R[2] = 2.f * (x * z + y * w);
-  R[3] = 2.f * (x * y + z * w);       R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - x * w);
-  R[6] = 2.f * (x * z - y * w);       R[7] = 2.f * (y * z + x * w);       R[8] = 1.f - 2.f * (x * x + y * y);
-}
-
-// the unit quaternion (xyzw, w >= 0) of a near-rotation R (row-major), Shepperd's branches; the normalisation re-orthonormalises R
-RP_DEV void rot_to_quat(const float (&R)[9], float (&q)[4]) {
-  const float tr = R[0] + R[4] + R[8];
-  float v[4];
-  if (tr > 0.f) {
-    v[3] = 1.f + tr; v[0] = R[7] - R[5]; v[1] = R[2] - R[6]; v[2] = R[3] - R[1];
-  } else if (R[0] >= R[4] && R[0] >= R[8]) {
-    v[0] = 1.f + R[0] - R[4] - R[8]; v[3] = R[7] - R[5]; v[1] = R[1] + R[3]; v[2] = R[2] + R[6];
-  } else if (R[4] >= R[8]) {
-    v[1] = 1.f + R[4] - R[0] - R[8]; v[3] = R[2] - R[6]; v[0] = R[1] + R[3]; v[2] = R[5] + R[7];
-  } else {
-    v[2] = 1.f + R[8] - R[0] - R[4]; v[3] = R[3] - R[1]; v[0] = R[2] + R[6]; v[1] = R[5] + R[7];
-  }
-  const float nrm = sqrtf(((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + v[3] * v[3]);
-  const float s = v[3] < 0.f ? -1.f : 1.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = nrm > 0.f ? s * v[i] / nrm : (i == 3 ? 1.f : 0.f);
-}
-
-// [a]x R, row-major
-RP_DEV void cross_times(const float (&a)[3], const float (&R)[9], float (&e)[9]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    e[c] = a[1] * R[6 + c] - a[2] * R[3 + c];
-    e[3 + c] = a[2] * R[c] - a[0] * R[6 + c];
-    e[6 + c] = a[0] * R[3 + c] - a[1] * R[c];
-  }
-}
-
-RP_DEV void cross3(const float (&a)[3], const float (&b)[3], float (&c)[3]) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 RP_DEV void matvec(const float (&m)[9], const float (&v)[3], float (&o)[3]) {
 #pragma unroll
   for (int r = 0; r < 3; ++r) o[r] = (m[3 * r] * v[0] + m[3 * r + 1] * v[1]) + m[3 * r + 2] * v[2];
@@ -617,7 +338,7 @@ __global__ __launch_bounds__(NT) void decompose_kernel(const float* __restrict__
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
     h[i] = H[b * 9 + i];
-    bad = bad || !(fabsf(h[i]) <= FINITE);
+    bad = bad || !(fabsf(h[i]) <= RP_FINITE);
   }
   const float ta = tau[b], tau2 = ta > 0.f ? ta * ta : 1.f;
   bad = bad || !(ta > 0.f);
@@ -627,7 +348,7 @@ __global__ __launch_bounds__(NT) void decompose_kernel(const float* __restrict__
   }
   float u[3][3], sg[3], v[3][3];
   svd3x3_dev(h, u, sg, v);
-  if (!(sg[1] > 0.f) || !(sg[1] >= RANK_MIN * sg[0]) || !(sg[0] <= FINITE)) {
+  if (!(sg[1] > 0.f) || !(sg[1] >= RANK_MIN * sg[0]) || !(sg[0] <= RP_FINITE)) {
     bad = true;                                    // (uniform) the identity and its factors: arithmetic below stays finite
 #pragma unroll
     for (int i = 0; i < 9; ++i) h[i] = i % 4 == 0 ? 1.f : 0.f;
@@ -679,8 +400,8 @@ __global__ __launch_bounds__(NT) void decompose_kernel(const float* __restrict__
     float uc[3], vc[3];
     const float u0[3] = {u[0][0], u[0][1], u[0][2]}, u1[3] = {u[1][0], u[1][1], u[1][2]};
     const float v0[3] = {v[0][0], v[0][1], v[0][2]}, v1[3] = {v[1][0], v[1][1], v[1][2]};
-    cross3(u0, u1, uc);
-    cross3(v0, v1, vc);
+    cross(u0, u1, uc);
+    cross(v0, v1, vc);
     const float sgn = s4[0] < 0.f ? -1.f : 1.f;    // u of -H is -u: the first two columns change sign, their cross product does not
 #pragma unroll
     for (int r = 0; r < 3; ++r)
@@ -707,9 +428,9 @@ __global__ __launch_bounds__(NT) void decompose_kernel(const float* __restrict__
       float uu[3], nn[3], hu[3], w3[3], R[9], q[4], td[3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) uu[i] = ca * v[0][i] + sb * v[2][i];
-      cross3(v2, uu, nn);
+      cross(v2, uu, nn);
       matvec(h, uu, hu);
-      cross3(hv2, hu, w3);
+      cross(hv2, hu, w3);
 #pragma unroll
       for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -729,7 +450,7 @@ __global__ __launch_bounds__(NT) void decompose_kernel(const float* __restrict__
       for (int s = 0; s < 2; ++s) {
         const int k = 2 * pair + s;
         const float sg_ = s == 0 ? 1.f : -1.f;
-        cvalid[k] = tn > 0.f && tn <= FINITE;
+        cvalid[k] = tn > 0.f && tn <= RP_FINITE;
         scale[k] = tn;
 #pragma unroll
         for (int i = 0; i < 3; ++i) { ct[k][i] = sg_ * tu[i]; cn[k][i] = sg_ * nn[i]; }
@@ -761,7 +482,7 @@ __global__ __launch_bounds__(NT) void decompose_kernel(const float* __restrict__
     cvalid[k] = cvalid[k] && !bad;
     vis[k] = rotation ? 1.f : s8[2 * k] / wcsum;
     cost[k] = rotation ? 0.f : s8[2 * k + 1] / wsum;
-    cvalid[k] = cvalid[k] && cost[k] <= FINITE;    // (false for a NaN, too)
+    cvalid[k] = cvalid[k] && cost[k] <= RP_FINITE;    // (false for a NaN, too)
     float* PO = pose + (b * 4 + k) * 7;
     float* NO = normal + (b * 4 + k) * 3;
     float* CS = cstat + (b * 4 + k) * 4;
@@ -799,20 +520,8 @@ extern "C" int rp_homography_abi_version(void) { return RP_HOMOGRAPHY_ABI_VERSIO
 extern "C" int rp_homography_consensus(const float* x1, const float* x2, const float* w, const float* tau, int seed, float* H, int* best,
                                        float* stat, float* w_out, float* hyp_H, float* hyp_cost, int* samples, int P, int M, int n,
                                        void* stream) {
-  if (n <= 0 || P < 4 || M < 1 || !x1 || !x2 || !tau || !H || !best || !stat || !hyp_H || !hyp_cost) return RP_EBADSHAPE;
-  if (P > RP_HOMOGRAPHY_MAX_P || M > RP_HOMOGRAPHY_MAX_M) return RP_EUNSUPPORTED;
-  const int chunks = (M + NT - 1) / NT;
-  if ((long long)n * chunks > 2147483647LL) return RP_EUNSUPPORTED;
-  if (((uintptr_t)x1 | (uintptr_t)x2) & 7) return RP_EALIGN;
-  if (((uintptr_t)w | (uintptr_t)tau | (uintptr_t)H | (uintptr_t)best | (uintptr_t)stat | (uintptr_t)w_out | (uintptr_t)hyp_H |
-       (uintptr_t)hyp_cost | (uintptr_t)samples) & 3)
-    return RP_EALIGN;
-  hipLaunchKernelGGL(hypothesis_kernel, dim3(n * chunks), dim3(NT), 0, (hipStream_t)stream, x1, x2, w, tau, (uint32_t)seed, hyp_H, hyp_cost,
-                     samples, P, M, chunks);
-  RP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(select_kernel, dim3(n), dim3(NT), 0, (hipStream_t)stream, x1, x2, w, tau, hyp_H, hyp_cost, H, best, stat, w_out, P, M);
-  RP_CHECK_LAUNCH();
-  return RP_OK;
+  return consensus_launch<4, RP_HOMOGRAPHY_MAX_P, RP_HOMOGRAPHY_MAX_M, hypothesis_kernel, select_kernel>(
+      x1, x2, w, tau, seed, H, best, stat, w_out, hyp_H, hyp_cost, samples, P, M, n, stream);
 }
 
 extern "C" int rp_homography_refine(const float* x1, const float* x2, const float* w, const float* tau, const float* H0, int iters,

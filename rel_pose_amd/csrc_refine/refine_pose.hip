@@ -9,14 +9,16 @@
 //   per iteration, TWO barriers:
 //     pass 1   residual s, exact Jacobian J [5] and Cauchy weight o of every owned row; the 15 upper entries of H = sum o J J^T and the
 //              5 of g = sum o J s in ONE fused 20-value reduction
-//     solve    (H + lambda diag H) delta = -g: diagonal scaling, 5 x 5 Cholesky, the retraction -- in every thread, redundantly: the sums
-//              are bit-identical in all 256 threads (csrc/block_sum.h), so the breakdown and accept decisions are uniform
+//     solve    (H + lambda diag H) delta = -g: diagonal scaling, 5 x 5 Cholesky (csrc/two_view.h), the retraction -- in every thread,
+//              redundantly: the sums are bit-identical in all 256 threads (csrc/block_sum.h), so the breakdown and accept decisions
+//              are uniform
 //     pass 2   the cost at the trial pose: one one-value reduction
 //   finish   the weights at the output pose (if asked for); thread 0 stores pose, E and stat
 // No atomics, no workspace; nothing is read from an output.  pose may alias pose0: every thread has read pose0 before the first
 // barrier, thread 0 writes pose behind the last.
 #include "../csrc/common.h"
 #include "../csrc/block_sum.h"
+#include "../csrc/two_view.h"
 #include "../../include/relpose_refine.h"
 
 namespace {
@@ -28,46 +30,6 @@ constexpr int ROWS = (MAXP + NT - 1) / NT;           // rows one thread owns: 7
 constexpr int RED = 20;                              // floats per wave in the reduction buffer: 15 of H + 5 of g
 constexpr float MIN_NORM = 1e-30f;                   // |t0| or |q0| below this: degenerate
 constexpr float LAMBDA0 = 1e-3f, LAMBDA_MIN = 1e-7f, LAMBDA_MAX = 1e7f;
-
-// v / |v| with the largest magnitude taken out first (no overflow, no underflow); returns |v| (0, or a NaN, for a v that has no direction)
-template <int N>
-RP_DEV float unit(const float (&v)[N], float (&u)[N]) {
-  float m = 0.f;
-#pragma unroll
-  for (int i = 0; i < N; ++i) m = fmaxf(m, fabsf(v[i]));
-  if (!(m > 0.f)) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) u[i] = v[i];
-    return 0.f;
-  }
-  float ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    u[i] = v[i] / m;
-    ss += u[i] * u[i];
-  }
-  const float s = sqrtf(ss);
-#pragma unroll
-  for (int i = 0; i < N; ++i) u[i] = u[i] / s;
-  return m * s;
-}
-
-RP_DEV void quat_to_rot(const float (&q)[4], float (&R)[9]) {
-  const float x = q[0], y = q[1], z = q[2], w = q[3];
-  R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - z * w);       R[2] = 2.f * (x * z + y * w);
-  R[3] = 2.f * (x * y + z * w);       R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - x * w);
-  R[6] = 2.f * (x * z - y * w);       R[7] = 2.f * (y * z + x * w);       R[8] = 1.f - 2.f * (x * x + y * y);
-}
-
-// [a]x R, row-major
-RP_DEV void cross_times(const float (&a)[3], const float (&R)[9], float (&e)[9]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    e[c] = a[1] * R[6 + c] - a[2] * R[3 + c];
-    e[3 + c] = a[2] * R[c] - a[0] * R[6 + c];
-    e[6 + c] = a[0] * R[3 + c] - a[1] * R[c];
-  }
-}
 
 // the basis of the tangent plane at the unit vector t: e_k of the smallest |t_k| (the lowest index on ties), b1 = normalise(e_k x t),
 // b2 = t x b1
@@ -129,62 +91,6 @@ RP_DEV void retract(const float (&t)[3], const float (&q)[4], const float (&b1)[
   const float tn = sqrtf((nt[0] * nt[0] + nt[1] * nt[1]) + nt[2] * nt[2]);
 #pragma unroll
   for (int i = 0; i < 3; ++i) t1[i] = nt[i] / tn;
-}
-
-// (H + lam diag H) delta = -g in the diagonally scaled form by Cholesky; false on a breakdown.  a: the 15 upper entries of H row by
-// row, then g.
-RP_DEV bool solve5(const float (&a)[RED], float lam, float (&delta)[5]) {
-  float H[5][5], sc[5], rhs[5];
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i)
-#pragma unroll
-    for (int j = i; j < 5; ++j) H[i][j] = H[j][i] = a[k++];
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    ok = ok && H[i][i] > 0.f && H[i][i] <= 3.0e38f;
-    sc[i] = 1.f / sqrtf(H[i][i]);
-    rhs[i] = a[15 + i] * sc[i];
-  }
-  if (!ok) return false;
-  float L[5][5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    float p = 1.f + lam;
-#pragma unroll
-    for (int m = 0; m < j; ++m) p = p - L[j][m] * L[j][m];
-    if (!(p > 0.f) || !(p <= 3.0e38f)) return false;
-    L[j][j] = sqrtf(p);
-#pragma unroll
-    for (int i = j + 1; i < 5; ++i) {
-      float v = H[i][j] * sc[i] * sc[j];
-#pragma unroll
-      for (int m = 0; m < j; ++m) v = v - L[i][m] * L[j][m];
-      L[i][j] = v / L[j][j];
-    }
-  }
-  float y[5], z[5];
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    float v = rhs[i];
-#pragma unroll
-    for (int m = 0; m < i; ++m) v = v - L[i][m] * y[m];
-    y[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = 4; i >= 0; --i) {
-    float v = y[i];
-#pragma unroll
-    for (int m = i + 1; m < 5; ++m) v = v - L[m][i] * z[m];
-    z[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    delta[i] = -(z[i] * sc[i]);
-    ok = ok && fabsf(delta[i]) <= 3.0e38f;
-  }
-  return ok;
 }
 
 __global__ __launch_bounds__(NT) void refine_pose_kernel(const float* pose0, const float* __restrict__ x1, const float* __restrict__ x2,
@@ -304,7 +210,7 @@ __global__ __launch_bounds__(NT) void refine_pose_kernel(const float* pose0, con
     block_sum(a, red, phase);
     // ---- the step and the trial pose (uniform)
     float delta[5], t1[3], q1[4], e1[9];
-    const bool solved = solve5(a, lam, delta);
+    const bool solved = lm_cholesky_solve(a, lam, delta);
     if (!solved) {
 #pragma unroll
       for (int i = 0; i < 5; ++i) delta[i] = 0.f;

@@ -11,6 +11,7 @@
 // No atomics, no workspace, no matrix instruction; nothing is read from an output.  Every loop has a fixed trip count.
 #include "../csrc/common.h"
 #include "../csrc/block_sum.h"
+#include "../csrc/two_view.h"
 #include "../../include/relpose_triangulate.h"
 
 namespace {
@@ -23,55 +24,6 @@ constexpr int RED = 6;                               // floats per wave in the r
 constexpr float MIN_NORM = 1e-30f;                   // |t| or |q| below this: degenerate
 constexpr float MIN_DEN = 1e-30f;                    // a denominator of the correction not above this: lambda = 0
 constexpr float INF_SIN2 = 1e-10f;                   // |g|^2 below this times |x2ch|^2 |r|^2: the row is at infinity
-constexpr float FINITE_MAX = 3.0e38f;
-
-// v / |v| with the largest magnitude taken out first (no overflow, no underflow); returns |v| (0, or a NaN, for a v that has no direction)
-template <int N>
-RP_DEV float unit(const float (&v)[N], float (&u)[N]) {
-  float m = 0.f;
-#pragma unroll
-  for (int i = 0; i < N; ++i) m = fmaxf(m, fabsf(v[i]));
-  if (!(m > 0.f)) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) u[i] = v[i];
-    return 0.f;
-  }
-  float ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    u[i] = v[i] / m;
-    ss += u[i] * u[i];
-  }
-  const float s = sqrtf(ss);
-#pragma unroll
-  for (int i = 0; i < N; ++i) u[i] = u[i] / s;
-  return m * s;
-}
-
-RP_DEV void quat_to_rot(const float (&q)[4], float (&R)[9]) {
-  const float x = q[0], y = q[1], z = q[2], w = q[3];
-  R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - z * w);       R[2] = 2.f * (x * z + y * w);
-  R[3] = 2.f * (x * y + z * w);       R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - x * w);
-  R[6] = 2.f * (x * z - y * w);       R[7] = 2.f * (y * z + x * w);       R[8] = 1.f - 2.f * (x * x + y * y);
-}
-
-// [a]x R, row-major
-RP_DEV void cross_times(const float (&a)[3], const float (&R)[9], float (&e)[9]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    e[c] = a[1] * R[6 + c] - a[2] * R[3 + c];
-    e[3 + c] = a[2] * R[c] - a[0] * R[6 + c];
-    e[6 + c] = a[0] * R[3 + c] - a[1] * R[c];
-  }
-}
-
-RP_DEV void cross(const float (&a)[3], const float (&b)[3], float (&c)[3]) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-RP_DEV float dot(const float (&a)[3], const float (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 __global__ __launch_bounds__(NT) void triangulate_kernel(const float* __restrict__ pose, const float* __restrict__ x1,
                                                           const float* __restrict__ x2, const float* __restrict__ w,
@@ -104,7 +56,7 @@ __global__ __launch_bounds__(NT) void triangulate_kernel(const float* __restrict
 #pragma unroll
   for (int i = 0; i < 7; ++i) {
     p0[i] = pose[b * 7 + i];
-    finite = finite && fabsf(p0[i]) <= FINITE_MAX;
+    finite = finite && fabsf(p0[i]) <= RP_FINITE;
   }
   const float t0[3] = {p0[0], p0[1], p0[2]}, q0[4] = {p0[3], p0[4], p0[5], p0[6]};
   const float tn = unit(t0, t), qn = unit(q0, q);

@@ -565,6 +565,39 @@ def test_shared_device_primitives_have_one_definition():
         assert len(holders) == 1, (needle, holders)
 
 
+def test_geometry_primitives_and_the_consensus_core_have_one_definition():
+    """The two-view primitives (csrc/two_view.h) and every shared stage of the hypothesise-and-verify libraries (csrc/consensus_core.h:
+    the LDS rows, the hash, Floyd's sampler, the argmin tree) exist ONCE over all csrc*/ directories: a solver file that brings its own
+    copy again fails here.  The sampler and the tie-breaking rule are a contract across the libraries, so there is one text to fix."""
+    pkg = os.path.join(ROOT, "rel_pose_amd")
+    texts = {}
+    for d in sorted(n for n in os.listdir(pkg) if n.startswith("csrc") and os.path.isdir(os.path.join(pkg, n))):
+        for name in sorted(os.listdir(os.path.join(pkg, d))):
+            if name.endswith((".hip", ".h")):
+                texts[d + "/" + name] = open(os.path.join(pkg, d, name)).read()
+    assert len({f.split("/")[0] for f in texts}) >= 9
+    one = {"csrc/consensus_core.h": (r"RP_DEV uint32_t mix\(", r"0x9E3779B9u", r"struct\s+\w*Rows\b", r"c == bc\[tid\] && i < bi\[tid\]",
+                                     r"\bint consensus_stage\(", r"\bvoid consensus_sample\(", r"\bfloat consensus_cost\(",
+                                     r"\bint consensus_select\(", r"\bint consensus_launch\("),
+           "csrc/two_view.h": (r"RP_DEV float sampson\(", r"void quat_to_rot\(", r"void rot_to_quat\(", r"void cross_times\(",
+                               r"RP_DEV float unit\(", r"void cross3?\(", r"RP_DEV float dot\(", r"void sign_rule\(", r"bool all_finite\(",
+                               r"bool normalise\w*\(", r"void null_vector_8x9\(", r"bool (lm_cholesky_solve|solve\d+)\(")}
+    for holder, needles in one.items():
+        for needle in needles:
+            assert [f for f, t in texts.items() if re.search(needle, t)] == [holder], needle
+    # the Householder null vector is not written out again either: its reflection loop is in the one header
+    assert [f for f, t in texts.items() if "copysignf(nrm, A[j][j])" in t] == ["csrc/two_view.h"]
+    for f in ("csrc_consensus/consensus.hip", "csrc_fivepoint/five_point.hip", "csrc_homography/homography.hip"):
+        assert '#include "../csrc/consensus_core.h"' in texts[f] and "consensus_launch<" in texts[f], f
+        for stage in ("consensus_stage(", "consensus_sample(", "consensus_cost(", "consensus_select("):
+            assert texts[f].count(stage) == 1, (f, stage)
+    for f in ("csrc_eightpoint/eight_point.hip", "csrc_refine/refine_pose.hip", "csrc_consensus/consensus.hip",
+              "csrc_fivepoint/five_point.hip", "csrc_homography/homography.hip", "csrc_triangulate/triangulate.hip"):
+        assert '#include "../csrc/two_view.h"' in texts[f], f
+    # the convention of block_sum.h: the headers declare no LDS, the __global__ functions do and pass it by reference
+    assert "__shared__" not in texts["csrc/consensus_core.h"] and "__shared__" not in texts["csrc/two_view.h"]
+
+
 def test_bf16_weight_copies_of_the_bf16_configuration():
     """Host side of the bf16 configuration's row-resident / fused-MLP kernels: ops.bf16_weight keeps a round-to-nearest-even bf16 copy of a
     weight until the weight is modified; ops._chunk_permuted_bf16 additionally stores the 768 hidden units of every 32-chunk in the order

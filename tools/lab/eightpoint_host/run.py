@@ -7,7 +7,6 @@ cannot show.
 
 The program is built with g++ in a temporary directory; nothing is written into the tree."""
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -17,32 +16,16 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(HERE)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.dirname(HERE)]
 warnings.simplefilter("ignore")
+import host_emu                               # noqa: E402
 from tests import _eightpoint_ref as R          # noqa: E402
 from tests import test_gpu_eightpoint as T      # noqa: E402
 
 TMP = tempfile.mkdtemp(prefix="eightpoint_host_")
 
 
-def build():
-    pkg = os.path.join(ROOT, "rel_pose_amd")
-    svd = open(os.path.join(pkg, "csrc", "svd3x3.h")).read().replace('#include "common.h"', '#include "shim.h"')
-    k = open(os.path.join(pkg, "csrc_eightpoint", "eight_point.hip")).read()
-    k = k.replace('#include "../csrc/common.h"', '#include "shim.h"').replace('#include "../csrc/svd3x3.h"', '#include "svd3x3.h"')
-    k = k.replace('#include "../csrc/block_sum.h"', '#include "block_sum.h"')
-    red = open(os.path.join(pkg, "csrc", "block_sum.h")).read().replace('#include "common.h"', '#include "shim.h"')
-    open(os.path.join(TMP, "block_sum.h"), "w").write(red)
-    k = re.sub(r'#include "../../include/(\w+\.h)"', r'#include "\1"', k)
-    open(os.path.join(TMP, "svd3x3.h"), "w").write(svd)
-    open(os.path.join(TMP, "kernel.cpp"), "w").write(k)
-    exe = os.path.join(TMP, "emu")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-w", "-fsanitize=address,undefined", "-I", TMP, "-I", HERE,
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "main.cpp"), "-o", exe])
-    return exe
-
-
-exe = build()
+exe = host_emu.build("csrc_eightpoint/eight_point.hip", HERE, TMP)
 IN, OUT = os.path.join(TMP, "in.bin"), os.path.join(TMP, "out.bin")
 
 

@@ -22,6 +22,7 @@ struct Idx { int x; };
 static Idx threadIdx, blockIdx;
 struct dim3 { int x; dim3(int a) : x(a) {} };
 struct float2 { float x, y; };
+static inline float2 make_float2(float x, float y) { return float2{x, y}; }
 typedef void* hipStream_t;
 static const int NTH = 256;
 static ucontext_t mainctx, ctx[NTH];

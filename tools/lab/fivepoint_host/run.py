@@ -8,7 +8,6 @@ kernel shuffles no fp64 value, so the shim needs no extension.
 
 The program is built with g++ in a temporary directory; nothing is written into the tree."""
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -17,10 +16,10 @@ import warnings
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(os.path.dirname(HERE), "eightpoint_host")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(HERE)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.dirname(HERE)]
 warnings.simplefilter("ignore")
+import host_emu                               # noqa: E402
 from tests import _consensus_ref as C           # noqa: E402
 from tests import _eightpoint_ref as R          # noqa: E402
 from tests import _fivepoint_ref as F           # noqa: E402
@@ -28,22 +27,7 @@ from tests import _fivepoint_ref as F           # noqa: E402
 TMP = tempfile.mkdtemp(prefix="fivepoint_host_")
 
 
-def build():
-    pkg = os.path.join(ROOT, "rel_pose_amd")
-    for h in ("svd3x3.h", "block_sum.h"):
-        open(os.path.join(TMP, h), "w").write(open(os.path.join(pkg, "csrc", h)).read().replace('#include "common.h"', '#include "shim.h"'))
-    k = open(os.path.join(pkg, "csrc_fivepoint", "five_point.hip")).read()
-    k = k.replace('#include "../csrc/common.h"', '#include "shim.h"')
-    k = re.sub(r'#include "../csrc/(\w+\.h)"', r'#include "\1"', k)
-    k = re.sub(r'#include "../../include/(\w+\.h)"', r'#include "\1"', k)
-    open(os.path.join(TMP, "kernel.cpp"), "w").write(k)
-    exe = os.path.join(TMP, "emu")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-w", "-fsanitize=address,undefined", "-I", TMP, "-I", SHIM,
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "main.cpp"), "-o", exe])
-    return exe
-
-
-exe = build()
+exe = host_emu.build("csrc_fivepoint/five_point.hip", HERE, TMP)
 IN, OUT = os.path.join(TMP, "in.bin"), os.path.join(TMP, "out.bin")
 
 

@@ -9,7 +9,6 @@ used; shim.h says what this can and cannot show.
 One program call runs the chain consensus -> refine (from the consensus winner) -> decomposition (of the refined H).  The program is
 built with g++ in a temporary directory; nothing is written into the tree."""
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -18,33 +17,17 @@ import warnings
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(os.path.dirname(HERE), "eightpoint_host")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(HERE)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.dirname(HERE)]
 warnings.simplefilter("ignore")
+import host_emu                               # noqa: E402
 from tests import _consensus_ref as C           # noqa: E402
 from tests import _homography_ref as H          # noqa: E402
 
 TMP = tempfile.mkdtemp(prefix="homography_host_")
 
 
-def build():
-    pkg = os.path.join(ROOT, "rel_pose_amd")
-    for h in ("svd3x3.h", "block_sum.h"):
-        open(os.path.join(TMP, h), "w").write(open(os.path.join(pkg, "csrc", h)).read().replace('#include "common.h"', '#include "shim.h"'))
-    k = open(os.path.join(pkg, "csrc_homography", "homography.hip")).read()
-    # (the shim's float2 is a plain aggregate: the one HIP helper this kernel uses beyond it is supplied here)
-    k = k.replace('#include "../csrc/common.h"', '#include "shim.h"\nstatic inline float2 make_float2(float x, float y) { return float2{x, y}; }')
-    k = re.sub(r'#include "../csrc/(\w+\.h)"', r'#include "\1"', k)
-    k = re.sub(r'#include "../../include/(\w+\.h)"', r'#include "\1"', k)
-    open(os.path.join(TMP, "kernel.cpp"), "w").write(k)
-    exe = os.path.join(TMP, "emu")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-w", "-fsanitize=address,undefined", "-I", TMP, "-I", SHIM,
-                           "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "main.cpp"), "-o", exe])
-    return exe
-
-
-exe = build()
+exe = host_emu.build("csrc_homography/homography.hip", HERE, TMP)
 IN, OUT = os.path.join(TMP, "in.bin"), os.path.join(TMP, "out.bin")
 
 

@@ -8,7 +8,6 @@ used; shim.h says what this can and cannot show.
 
 The program is built with g++ in a temporary directory; nothing is written into the tree."""
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -17,30 +16,16 @@ import warnings
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(os.path.dirname(HERE), "eightpoint_host")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(HERE)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.dirname(HERE)]
 warnings.simplefilter("ignore")
+import host_emu                               # noqa: E402
 from tests import _triangulate_ref as T         # noqa: E402
 
 TMP = tempfile.mkdtemp(prefix="triangulate_host_")
 
 
-def build():
-    pkg = os.path.join(ROOT, "rel_pose_amd")
-    open(os.path.join(TMP, "block_sum.h"), "w").write(open(os.path.join(pkg, "csrc", "block_sum.h")).read().replace('#include "common.h"', '#include "shim.h"'))
-    k = open(os.path.join(pkg, "csrc_triangulate", "triangulate.hip")).read()
-    k = k.replace('#include "../csrc/common.h"', '#include "shim.h"')
-    k = re.sub(r'#include "../csrc/(\w+\.h)"', r'#include "\1"', k)
-    k = re.sub(r'#include "../../include/(\w+\.h)"', r'#include "\1"', k)
-    open(os.path.join(TMP, "kernel.cpp"), "w").write(k)
-    exe = os.path.join(TMP, "emu")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", TMP,
-                           "-I", SHIM, "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "main.cpp"), "-o", exe])
-    return exe
-
-
-exe = build()
+exe = host_emu.build("csrc_triangulate/triangulate.hip", HERE, TMP, flags=("-fno-sanitize-recover=undefined",))
 IN, OUT = os.path.join(TMP, "in.bin"), os.path.join(TMP, "out.bin")
 
 
