@@ -187,7 +187,8 @@ int rp_maxpool3x3s2_bwd(const void* dy, const unsigned char* idx, void* dx, int 
 /* The stem convolution (torchvision resnet.conv1: 7x7, stride 2, pad 3, 3 -> 64, no bias; src/model.py:127), forward, hand-written
  * implicit GEMM (csrc/conv_stem.hip).  x_padded [N, H+6, W+6, 3]: the channels-last image inside a 3-pixel zero frame; w [64,7,7,3]
  * (the memory of a channels-last nn.Conv2d weight); y [N, (H-1)/2+1, (W-1)/2+1, 64].  W must be even (the pad taps of the last
- * window stay inside its row).  stats (optional) [rp_conv_stem_blocks(N,H,W)][2][64] doubles: per-workgroup sums of y and y^2 per
+ * window stay inside its row): an odd W is refused with RP_EBADSHAPE before anything is launched, y and stats stay untouched; an odd H is
+ * accepted.  stats (optional) [rp_conv_stem_blocks(N,H,W)][2][64] doubles: per-workgroup sums of y and y^2 per
  * channel -- the following BatchNorm's batch statistics without a pass over y: rp_bn_stats_from_partials(stats, blocks, N*OH*OW, 64,
  * zeros, ...) finishes them (any partial sums of (x - pivot), (x - pivot)^2 over disjoint row sets are accepted). */
 int rp_conv_stem_blocks(int N, int H, int W);
@@ -195,7 +196,7 @@ int rp_conv_stem_fwd(const float* x_padded, const float* w, float* y, double* st
 
 /* The stem convolution of the bf16 configuration (csrc/conv_stem_bf16.hip): same operands as rp_conv_stem_fwd -- the fp32 image inside its
  * zero frame and the fp32 filter are rounded to bf16 on chip (v_mfma_f32_16x16x32_bf16, fp32 accumulate) -- y [N,OH,OW,64] bf16; stats as
- * above, of the stored bf16 values. */
+ * above, of the stored bf16 values.  Odd W is refused in the same way. */
 int rp_conv_stem_bf16_blocks(int N, int H, int W);
 int rp_conv_stem_fwd_bf16(const float* x_padded, const float* w, void* y, double* stats, int N, int H, int W, void* stream);
 /* ... and its weight gradient (csrc/conv_stem_wgrad_bf16.hip): dw [64][7][7][3] fp32 from the same framed fp32 image and dY [N,112,112,64]
