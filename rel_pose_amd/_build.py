@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so and librelpose_triangulate.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so, librelpose_triangulate.so and librelpose_conv5x5.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -40,6 +40,11 @@ HOMOGRAPHY_SOURCES = ["homography.hip"]
 TRIANGULATE_CSRC = os.path.join(HERE, "csrc_triangulate")
 TRIANGULATE_LIB = os.path.join(HERE, "librelpose_triangulate.so")
 TRIANGULATE_SOURCES = ["triangulate.hip"]
+# the 5x5 input-gradient library (include/relpose_conv5x5.h): a tenth library, the same pattern; the one kernel of the hot path that
+# lives outside csrc/ (the main library's surface stays what it was)
+CONV5X5_CSRC = os.path.join(HERE, "csrc_conv5x5")
+CONV5X5_LIB = os.path.join(HERE, "librelpose_conv5x5.so")
+CONV5X5_SOURCES = ["conv5x5_dgrad_f32.hip"]
 ARCH = "gfx950"
 
 
@@ -93,10 +98,14 @@ def triangulate_needs_build():
     return _stale(TRIANGULATE_LIB, TRIANGULATE_CSRC, TRIANGULATE_SOURCES, _triangulate_headers())
 
 
+def conv5x5_needs_build():
+    return _stale(CONV5X5_LIB, CONV5X5_CSRC, CONV5X5_SOURCES, _conv5x5_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All nine libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All ten libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -119,6 +128,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, HOMOGRAPHY_LIB, HOMOGRAPHY_CSRC, HOMOGRAPHY_SOURCES, _homography_headers())
             if force or triangulate_needs_build():
                 _build_locked(verbose, force, TRIANGULATE_LIB, TRIANGULATE_CSRC, TRIANGULATE_SOURCES, _triangulate_headers())
+            if force or conv5x5_needs_build():
+                _build_locked(verbose, force, CONV5X5_LIB, CONV5X5_CSRC, CONV5X5_SOURCES, _conv5x5_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -159,6 +170,10 @@ def _homography_headers():
 
 def _triangulate_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_triangulate.h")]
+
+
+def _conv5x5_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_conv5x5.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

@@ -182,6 +182,15 @@ TRIANGULATE_MAX_P = _TRIANGULATE_CONSTS["RP_TRIANGULATE_MAX_P"]
 TRIANGULATE_EXPORTS = tuple(_TRIANGULATE_PROTOTYPES)
 
 
+# the 5x5 input-gradient library (include/relpose_conv5x5.h -> librelpose_conv5x5.so): the same parser, errcheck and RP_E* codes a tenth time
+_CONV5X5_LIB = None
+CONV5X5_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_conv5x5.h")
+with open(CONV5X5_HEADER) as _f:
+    _CONV5X5_CONSTS, _, _CONV5X5_PROTOTYPES, _CONV5X5_STATUS = _header_contract(_f.read(), "relpose_conv5x5.h")
+CONV5X5_ABI_VERSION = _CONV5X5_CONSTS["RP_CONV5X5_ABI_VERSION"]
+CONV5X5_EXPORTS = tuple(_CONV5X5_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -423,6 +432,32 @@ def load_triangulate():
         if name in _TRIANGULATE_STATUS:
             fn.errcheck = _raise_on_status
     _TRIANGULATE_LIB = lib
+    return lib
+
+
+def load_conv5x5():
+    """Load (building if absent or stale) and type librelpose_conv5x5.so.  Raises on any failure: there is no fallback."""
+    global _CONV5X5_LIB
+    if _CONV5X5_LIB is not None:
+        return _CONV5X5_LIB
+    path = _build.CONV5X5_LIB
+    if _build.conv5x5_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_conv5x5_abi_version.restype = c_int
+    if lib.rp_conv5x5_abi_version() != CONV5X5_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_conv5x5_abi_version(), CONV5X5_ABI_VERSION))
+    for name, (res, args) in _CONV5X5_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _CONV5X5_STATUS:
+            fn.errcheck = _raise_on_status
+    _CONV5X5_LIB = lib
     return lib
 
 

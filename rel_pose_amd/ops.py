@@ -2180,6 +2180,71 @@ def conv3x3_c128_f32_ok(m, x):
             and getattr(m, "padding_mode", "zeros") == "zeros" and tuple(x.shape[1:]) == (128, 28, 28) and x.shape[0] >= CONV3X3_C128_F32_MIN_N)
 
 
+# The input gradients of the two valid 5x5 convolutions of extractor_final_conv (conv2 192 -> 192, downsample.0 128 -> 192, 28 x 28 maps) on
+# csrc_conv5x5/conv5x5_dgrad_f32.hip (librelpose_conv5x5.so); forward, weight and bias gradients stay on MIOpen.
+# RP_CONV5X5_DGRAD_F32=0: MIOpen for all of it (A/B aid).
+CONV5X5_DGRAD_F32 = os.environ.get("RP_CONV5X5_DGRAD_F32", "1") != "0"
+# A workgroup of the kernel owns one pixel of 128 images, so a launch costs the same for 1 and for 128 images: the own kernel is taken
+# when the LAST block of 128 images holds at least this many (profiles/conv5x5_dgrad_time.txt has the crossing).
+CONV5X5_DGRAD_F32_MIN_N = int(os.environ.get("RP_CONV5X5_DGRAD_F32_MIN_N", "112"))
+CONV5X5_DGRAD_IMAGES = 128
+
+
+def conv5x5_dgrad_f32(dy_nhwc, w_ohwi, res_nhwc=None):
+    """rp_conv5x5_dgrad_f32: dx [N,28,28,CI] (NHWC) = (res +) the input gradient of the valid 5x5 convolution with forward weight w
+    [192,5,5,CI] (the memory of a channels-last [192,CI,5,5] weight), CI = 128 or 192, for dy [N,24,24,192] (NHWC), exact fp32."""
+    lib = _lib.load_conv5x5()
+    if not (dy_nhwc.is_cuda and dy_nhwc.is_contiguous() and dy_nhwc.dtype == torch.float32 and dy_nhwc.dim() == 4
+            and tuple(dy_nhwc.shape[1:]) == (24, 24, 192) and dy_nhwc.shape[0] >= 1):
+        raise RuntimeError("conv5x5_dgrad_f32: contiguous fp32 [N,24,24,192] GPU tensor expected")
+    CI = w_ohwi.shape[-1]
+    if not (w_ohwi.is_cuda and w_ohwi.is_contiguous() and w_ohwi.dtype == torch.float32 and tuple(w_ohwi.shape[:3]) == (192, 5, 5)
+            and CI in (128, 192)):
+        raise RuntimeError("conv5x5_dgrad_f32: contiguous fp32 [192,5,5,128 | 192] GPU filter expected")
+    N = dy_nhwc.shape[0]
+    if res_nhwc is not None and not (res_nhwc.is_cuda and res_nhwc.is_contiguous() and res_nhwc.dtype == torch.float32
+                                     and tuple(res_nhwc.shape) == (N, 28, 28, CI)):
+        raise RuntimeError("conv5x5_dgrad_f32: contiguous fp32 [N,28,28,CI] GPU residual expected")
+    dx = torch.empty(N, 28, 28, CI, device=dy_nhwc.device, dtype=torch.float32)
+    # no timed(...) bracket: every timed tag needs an entry in bench.py's TAG_SYMBOLS, and that table is not this library's to extend
+    lib.rp_conv5x5_dgrad_f32(_p(dy_nhwc), _p(w_ohwi), _p(dx), N, CI, _p(res_nhwc), _st())
+    return dx
+
+
+class Conv5x5ValidF32Fn(_Fn):
+    """forward on MIOpen (F.conv2d on channels-last operands, as nn.Conv2d runs it); input gradient on rp_conv5x5_dgrad_f32; weight /
+    bias gradients on MIOpen"""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return torch.nn.functional.conv2d(x, w, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dx = dw = db = None
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        if ctx.needs_input_grad[0]:
+            dx = conv5x5_dgrad_f32(_nhwc(dy), _nhwc(w)).permute(0, 3, 1, 2)
+        mask = [False, bool(ctx.needs_input_grad[1]), ctx.has_bias and bool(ctx.needs_input_grad[2])]
+        if any(mask):
+            g = torch.ops.aten.convolution_backward(dy, x, w, [192] if ctx.has_bias else None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, mask)
+            dw = g[1] if mask[1] else None
+            db = g[2] if mask[2] else None
+        return dx, dw, db
+
+
+def conv5x5_dgrad_f32_ok(m, x):
+    n = x.shape[0]
+    return (CONV5X5_DGRAD_F32 and CNN_PRECISION == 0 and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
+            and x.requires_grad and tuple(m.kernel_size) == (5, 5) and m.stride == (1, 1) and m.padding == (0, 0) and m.dilation == (1, 1)
+            and m.groups == 1 and m.weight.shape[0] == 192 and tuple(x.shape[1:]) in ((192, 28, 28), (128, 28, 28))
+            and tuple(m.weight.shape[1:]) == (x.shape[1], 5, 5) and n >= CONV5X5_DGRAD_F32_MIN_N
+            and (n - 1) % CONV5X5_DGRAD_IMAGES + 1 >= CONV5X5_DGRAD_F32_MIN_N)
+
+
 def conv3x3_wgrad_f32_ok(m, x):
     return (CONV3X3_WGRAD_F32 and CNN_PRECISION == 0 and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
             and m.weight.requires_grad and tuple(m.weight.shape) == (64, 64, 3, 3) and m.bias is None and m.stride == (1, 1)
@@ -2219,6 +2284,8 @@ def conv2d(m, x, want_stats=False):
             return Conv3x3C64F32Fn.apply(x, m.weight, False, False, None)
         if conv3x3_c128_f32_ok(m, x):
             return Conv3x3C128F32Fn.apply(x, m.weight, m.bias, False)
+        if conv5x5_dgrad_f32_ok(m, x):
+            return Conv5x5ValidF32Fn.apply(x, m.weight, m.bias)
         return m(x)
     bf = torch.bfloat16
     ready = getattr(m, "_rp_bf16", None)
