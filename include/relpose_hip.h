@@ -43,8 +43,8 @@ extern "C" {
  * functions this header declares.  rp_abi_version() / rp_abi_export_count() return the values the library was COMPILED with, so a
  * binding (rel_pose_amd/_lib.py parses both macros and counts the declarations) rejects a stale .so at load time instead of
  * failing later on a missing symbol. */
-#define RP_ABI_VERSION 26
-#define RP_ABI_EXPORTS 110
+#define RP_ABI_VERSION 27
+#define RP_ABI_EXPORTS 112
 int rp_abi_version(void);
 int rp_abi_export_count(void);
 const char* rp_target_arch(void);
@@ -562,8 +562,13 @@ int rp_pose_normalize_bwd(const float* pred, const float* dout, float* dpred, in
  * six 8-element MFMA operands are loaded as they lie, e.g. the bf16 attention output into proj), bit 1 = y and y_pre are written as
  * bf16, bit 2 = dact_aux holds bf16, bit 3 = xn_out is written as bf16 (the rounded rows the MFMA consumed: what the bf16 weight-
  * gradient product reads).  The bits select the bf16 data path of BASELINE.json configs[4].
+ * rp_linear_rows192_grid: the number G of workgroups the launch with this M, N, form (ln != 0: the fused LayerNorm) and precision
+ * uses, 0 for arguments the entry point refuses.  The work list of (M / tile rows, rounded up) x (N / 32) items, tile-major, is cut into
+ * G contiguous ranges, the first (items % G) of them one item longer: G = min(items, resident workgroup slots of the device), so which
+ * ranges start inside a tile or run across a tile boundary depends on the device -- the query is how a test learns it.
  * ------------------------------------------------------------------------------------------- */
 int rp_linear_rows192_tile_rows(void);
+int rp_linear_rows192_grid(int M, int N, int ln, int precision);
 int rp_linear_rows192(const float* x, const float* w, const float* bias, const float* residual, const float* ln_gamma,
                       const float* ln_beta, float eps, float* y, float* y_pre, float* xn_out, float* mean_out, float* rstd_out,
                       const float* dact_aux, float* colsum_part, int M, int N, int K, int act, int precision, int io_bf16,
@@ -583,8 +588,14 @@ int rp_linear_rows192(const float* x, const float* w, const float* bias, const f
  * bit 3 = xn_out is written as bf16 (the rounded rows the fc1 product consumed; what the bf16 weight-gradient kernel rp_dw192_bf16 reads).
  * bit 4 (training and inference forms) = w2 is stored CHUNK-MAJOR, [hidden / 32][dim][32] (every staged tile 12 KB contiguous) instead of
  * [dim][hidden].
+ * rp_mlp_fused_grid: the number G of workgroups of the launch that rp_mlp_fused_fwd (backward = 0; train != 0: the training form) or
+ * rp_mlp_fused_bwd / rp_mlp_fused_bwd_ln (backward != 0; train ignored) makes for M rows at this precision, 0 for M <= 0 or an unknown
+ * precision.  The (row tile) x (24 chunks) list, tile-major, is cut into G contiguous ranges, the first (items % G) one item longer;
+ * G = min(items, resident workgroup slots).  A tile whose 24 chunks lie in one range is finished by that workgroup, every other tile
+ * by the fix-up launch from the partials of the ranges that share it.  Row tiles: 192 rows, except 64 for the fp32 forward.
  * ------------------------------------------------------------------------------------------- */
 size_t rp_mlp_fused_workspace_bytes(int M);
+int rp_mlp_fused_grid(int M, int backward, int train, int precision);
 int rp_mlp_fused_fwd(const float* x, const float* gamma, const float* beta, const float* w1, const float* b1, const float* w2,
                      const float* b2, float* y, void* workspace, int M, int dim, int hidden, float eps, float* xn_out, float* mean_out,
                      float* rstd_out, float* h_out, float* hpre_out, int precision, int io_bf16, void* stream);

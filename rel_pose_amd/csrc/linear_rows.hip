@@ -364,9 +364,21 @@ int rows_slots() {
   return slots;
 }
 
+// workgroups of a launch: one per resident slot of the form's kernel, or one per work item when there are fewer items than slots
+int rows_grid(int M, int N, bool ln, bool bf) {
+  const long long items = (long long)((M + ROWS - 1) / ROWS) * (N / CH);
+  const int slots = bf ? (ln ? rows_slots<true, true>() : rows_slots<false, true>()) : (ln ? rows_slots<true, false>() : rows_slots<false, false>());
+  return (int)(items < slots ? items : slots);
+}
+
 }  // namespace
 
 extern "C" int rp_linear_rows192_tile_rows(void) { return ROWS; }
+
+extern "C" int rp_linear_rows192_grid(int M, int N, int ln, int precision) {
+  if (M <= 0 || N <= 0 || N % CH != 0 || N > MAXN || (precision != 0 && precision != 1)) return 0;
+  return rows_grid(M, N, ln != 0, precision == 1);
+}
 
 extern "C" int rp_linear_rows192(const float* x, const float* w, const float* bias, const float* residual, const float* ln_gamma,
                                  const float* ln_beta, float eps, float* y, float* y_pre, float* xn_out, float* mean_out,
@@ -382,8 +394,7 @@ extern "C" int rp_linear_rows192(const float* x, const float* w, const float* bi
   const bool bf = precision == 1;
   RowsP p{x, w, bias, residual, ln_gamma, ln_beta, y, y_pre, xn_out, mean_out, rstd_out, dact_aux, colsum_part, M, N, eps, act, N / CH, (M + ROWS - 1) / ROWS, 0, 0, io_bf16};
   const long long items = (long long)p.tiles * p.nchunk;
-  const int slots = bf ? (ln ? rows_slots<true, true>() : rows_slots<false, true>()) : (ln ? rows_slots<true, false>() : rows_slots<false, false>());
-  const int G = (int)(items < slots ? items : slots);
+  const int G = rows_grid(M, N, ln, bf);
   p.base = (int)(items / G);
   p.rem = (int)(items % G);
   hipStream_t st = (hipStream_t)stream;

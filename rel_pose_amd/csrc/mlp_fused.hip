@@ -680,9 +680,10 @@ struct Variant {
     const long long items = (long long)tiles * NCHUNK;
     return (int)(items < slots ? items : slots);
   }
+  static int grid_of(int M) { return grid((M + ROWS - 1) / ROWS); }      // (rp_mlp_fused_grid: the G of partition())
   static int partition(MlpP& p) {
     p.tiles = (p.M + ROWS - 1) / ROWS;
-    const int G = grid(p.tiles), items = p.tiles * NCHUNK;
+    const int G = grid_of(p.M), items = p.tiles * NCHUNK;
     p.base = items / G;
     p.rem = items % G;
     p.P = (p.base + 1 + NCHUNK - 1) / NCHUNK + 1;                 // row tiles one range can touch
@@ -717,6 +718,29 @@ int mlp_variant() {
   return v;
 }
 
+// The ONE place that says which Variant a call selects: the launches and rp_mlp_fused_grid both go through it, so the query cannot
+// report another variant's partition.  f is called with a value of the selected Variant type.
+template <class F>
+int with_fwd_variant(bool train, int precision, F&& f) {
+  if (precision == 1) return train ? f(Variant<12, 3, 0, true, true>{}) : f(Variant<12, 3, 0, true, false>{});
+  if (train) {
+    switch (mlp_variant()) {
+      case 1: return f(Variant<8, 2, 0, false, true>{});
+      case 2: return f(Variant<12, 3, 0, false, true>{});
+      default: return f(Variant<4, 3, 0, false, true>{});
+    }
+  }
+  switch (mlp_variant()) {
+    case 1: return f(Variant<8, 2, 0>{});
+    case 2: return f(Variant<12, 3, 0>{});
+    default: return f(Variant<4, 3, 0>{});
+  }
+}
+template <class F>
+int with_bwd_variant(int precision, F&& f) {      // (both: 192-row tiles, same workspace / tile rows)
+  return precision == 1 ? f(Variant<12, 3, 1, true>{}) : f(Variant<12, 3, 1>{});
+}
+
 }  // namespace
 
 extern "C" size_t rp_mlp_fused_workspace_bytes(int M) {
@@ -742,19 +766,7 @@ extern "C" int rp_mlp_fused_fwd(const float* x, const float* gamma, const float*
   MlpP p{x, gamma, beta, w1, b1, w2, b2, y, nullptr, hpre_out, nullptr, (float*)workspace, M, eps, 0, 0, 0, 0, io_bf16,
          xn_out, mean_out, rstd_out, h_out};
   hipStream_t st = (hipStream_t)stream;
-  if (precision == 1) return train ? Variant<12, 3, 0, true, true>::launch(p, st) : Variant<12, 3, 0, true, false>::launch(p, st);
-  if (train) {
-    switch (mlp_variant()) {
-      case 1: return Variant<8, 2, 0, false, true>::launch(p, st);
-      case 2: return Variant<12, 3, 0, false, true>::launch(p, st);
-      default: return Variant<4, 3, 0, false, true>::launch(p, st);
-    }
-  }
-  switch (mlp_variant()) {
-    case 1: return Variant<8, 2, 0>::launch(p, st);
-    case 2: return Variant<12, 3, 0>::launch(p, st);
-    default: return Variant<4, 3, 0>::launch(p, st);
-  }
+  return with_fwd_variant(train, precision, [&](auto v) { return decltype(v)::launch(p, st); });
 }
 
 // Backward-data of the MLP (training): dhp [M,768] = (dy W2) o GELU'(hpre), dxn [M,192] = dhp W1, colpart [tiles,768] = column
@@ -765,10 +777,16 @@ extern "C" int rp_mlp_fused_fwd(const float* x, const float* gamma, const float*
 // operands are 8 more live registers).
 extern "C" size_t rp_mlp_fused_bwd_workspace_bytes(int M) { return M <= 0 ? 0 : Variant<12, 3, 1>::workspace(M); }
 extern "C" int rp_mlp_fused_bwd_tile_rows(void) { return Variant<12, 3, 1>::ROWS; }
+// workgroups (= contiguous ranges of the (row tile) x (chunk) list) of the launch the same arguments select in rp_mlp_fused_fwd
+// (backward = 0; train = the training form) or rp_mlp_fused_bwd / _bwd_ln (backward != 0)
+extern "C" int rp_mlp_fused_grid(int M, int backward, int train, int precision) {
+  if (M <= 0 || (precision != 0 && precision != 1)) return 0;
+  auto grid = [&](auto v) { return decltype(v)::grid_of(M); };
+  return backward ? with_bwd_variant(precision, grid) : with_fwd_variant(train != 0, precision, grid);
+}
 extern "C" int rp_mlp_fused_bwd_ln_part_rows(int M) { return M <= 0 ? 0 : (M + rp_mlp_fused_bwd_tile_rows() - 1) / rp_mlp_fused_bwd_tile_rows() * LN_SUB; }
 static int mlp_bwd_launch(MlpP p, int precision, hipStream_t st) {
-  if (precision == 1) return Variant<12, 3, 1, true>::launch(p, st);      // (same 192-row tiles: same workspace / tile rows)
-  return Variant<12, 3, 1>::launch(p, st);
+  return with_bwd_variant(precision, [&](auto v) { return decltype(v)::launch(p, st); });
 }
 extern "C" int rp_mlp_fused_bwd_ln(const float* dy, const float* hpre, const float* w2t, const float* w1t, float* dhp, float* dx,
                                    float* colpart, void* workspace, int M, int dim, int hidden, int precision, int io_bf16,
@@ -789,6 +807,5 @@ extern "C" int rp_mlp_fused_bwd(const float* dy, const float* hpre, const float*
   if ((precision != 0 && precision != 1) || (io_bf16 && (precision != 1 || (io_bf16 & ~22)))) return RP_EUNSUPPORTED;
   MlpP p{dy, nullptr, nullptr, w2t, nullptr, w1t, nullptr, dxn, hpre, dhp, colpart, (float*)workspace, M, 0.f, 0, 0, 0, 0, io_bf16,
          nullptr, nullptr, nullptr, nullptr};
-  if (precision == 1) return Variant<12, 3, 1, true>::launch(p, (hipStream_t)stream);      // (same 192-row tiles: same workspace / tile rows)
-  return Variant<12, 3, 1>::launch(p, (hipStream_t)stream);
+  return mlp_bwd_launch(p, precision, (hipStream_t)stream);
 }

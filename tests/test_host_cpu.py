@@ -155,9 +155,10 @@ def test_status_is_checked_where_work_is_launched_and_nowhere_else():
     assert hooked == launches and len(launches) == 76
     assert all(getattr(lib, n).restype is c_int for n in hooked)
     counts = {n for n in _lib.EXPORTS if getattr(lib, n).restype is c_int} - hooked
-    assert len(counts) == 18 and {"rp_abi_version", "rp_abi_export_count", "rp_bn_partial_blocks", "rp_dw192_f32_splits",
-                                  "rp_linear_rows192_tile_rows", "rp_mlp_fused_bwd_ln_part_rows"} <= counts
-    assert all(n.endswith(("_blocks", "_splits", "_tile_rows", "_part_rows")) for n in counts - {"rp_abi_version", "rp_abi_export_count"})
+    assert len(counts) == 20 and {"rp_abi_version", "rp_abi_export_count", "rp_bn_partial_blocks", "rp_dw192_f32_splits",
+                                  "rp_linear_rows192_tile_rows", "rp_mlp_fused_bwd_ln_part_rows", "rp_linear_rows192_grid",
+                                  "rp_mlp_fused_grid"} <= counts
+    assert all(n.endswith(("_blocks", "_splits", "_tile_rows", "_part_rows", "_grid")) for n in counts - {"rp_abi_version", "rp_abi_export_count"})
     assert not {n for n in hooked if n.startswith("rp_event_") or n.endswith("_workspace_bytes")}
     hook = lib.rp_gemm.errcheck
     fn = types.SimpleNamespace(__name__="rp_stand_in")
