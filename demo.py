@@ -120,7 +120,18 @@ def main(argv=None):
                          "chain, or with --consensus M the consensus chain) -- an ASCII PLY of the points in front of both cameras whose "
                          "Cauchy weight is at least 0.5, coloured from image 1, and one line with the reprojection cost, the front share "
                          "and the mean parallax; OUT.npz writes the arrays instead")
+    ap.add_argument("--guided", type=float, default=0.0, metavar="BAND",
+                    help="with --eight_point: guided matching (rel_pose_amd/guided.py) -- every token's partner searched again within BAND "
+                         "token pitches of the prior's epipolar lines, the pose refined on those matches; prints the guided pose and the "
+                         "share of the attention's mass that the regressed, the consensus and the guided pose explain, on one scale")
+    ap.add_argument("--prior", choices=("consensus", "regressed"), default=None, help="with --guided: the pose that guides (default consensus)")
     args = ap.parse_args(argv)
+    if args.guided and not args.eight_point:
+        ap.error("--guided needs --eight_point")
+    if args.guided < 0:
+        ap.error("--guided takes a positive band in token pitches")
+    if args.prior and not args.guided:
+        ap.error("--prior needs --guided")
     if args.points and not args.eight_point:
         ap.error("--points needs --eight_point")
     if args.subtoken and not (args.eight_point or args.matches):
@@ -168,6 +179,8 @@ def main(argv=None):
         print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine, args.consensus, args.seed, args.subtoken, args.minimal or "eight")
         if args.planar:
             print_planar(model, images, intr, png_size(args.img1), args.consensus or 256, args.seed, args.subtoken)
+        if args.guided:
+            print_guided(model, images, intr, png_size(args.img1), preds, est[0].data[:, 1], args.guided, args.prior or "consensus", args.subtoken)
         if args.points:
             write_points(model, images, intr, png_size(args.img1), args.points, args.refine or 10, args.consensus, args.seed, args.subtoken,
                          args.minimal or "eight")
@@ -257,6 +270,22 @@ def print_planar(model, images, intr, orig_hw, hypotheses=256, seed=0, subtoken=
     else:
         print("planar: candidate %d, %s" % (pick[0], "the only one that sees the plane from both cameras" if cs[pick[0], 0] >= 0.99
                                              else "by Sampson cost: none sees every match"))
+
+
+def print_guided(model, images, intr, orig_hw, regressed, regressed_raw, band, prior="consensus", subtoken=None):
+    """--guided BAND: one pose line of the usual form for the guided chain (prior -> matches within BAND token pitches of its epipolar
+    lines -> refinement from the prior), one with the share of its owners that found no partner in the band, and one with the in-band
+    share of the attention's mass under the regressed, the consensus and the guided pose (mean over both images and the heads).  The
+    guided matches lie near the prior's lines by construction, so the support, not the Sampson cost, is what says whether a pose holds."""
+    H, W = images.shape[-2:]
+    sy, sx = H / orig_hw[0], W / orig_hw[1]
+    K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
+    g = model.guided_pose_from_matches(images, K, prior=prior, band=band, subtoken=subtoken)
+    cons = g.prior if prior == "consensus" else model.consensus_pose_from_matches(images, K, subtoken=subtoken).pose
+    _angles_line("guided", g.pose[0].double().cpu(), torch.from_numpy(np.asarray(regressed, dtype=np.float64)))
+    print("guided: prior %s, band %g token pitches, %.4f of the owners without a partner in the band" % (prior, band, float(g.unmatched[0])))
+    sup = [float(model.pose_support(images, K, p, band=band).mean()) for p in (regressed_raw, cons)] + [float(g.support_after.mean())]
+    print("in-band share of the attention's mass: regressed %.4f, consensus %.4f, guided %.4f" % tuple(sup))
 
 
 def write_points(model, images, intr, orig_hw, path, refine=10, consensus=0, seed=0, subtoken=None, minimal="eight"):

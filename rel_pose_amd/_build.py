@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so, librelpose_triangulate.so and librelpose_conv5x5.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so, librelpose_triangulate.so, librelpose_conv5x5.so and librelpose_guided.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -45,6 +45,10 @@ TRIANGULATE_SOURCES = ["triangulate.hip"]
 CONV5X5_CSRC = os.path.join(HERE, "csrc_conv5x5")
 CONV5X5_LIB = os.path.join(HERE, "librelpose_conv5x5.so")
 CONV5X5_SOURCES = ["conv5x5_dgrad_f32.hip"]
+# the guided-matching library (include/relpose_guided.h): an eleventh library, the same pattern
+GUIDED_CSRC = os.path.join(HERE, "csrc_guided")
+GUIDED_LIB = os.path.join(HERE, "librelpose_guided.so")
+GUIDED_SOURCES = ["emm_guided.hip"]
 ARCH = "gfx950"
 
 
@@ -102,10 +106,14 @@ def conv5x5_needs_build():
     return _stale(CONV5X5_LIB, CONV5X5_CSRC, CONV5X5_SOURCES, _conv5x5_headers())
 
 
+def guided_needs_build():
+    return _stale(GUIDED_LIB, GUIDED_CSRC, GUIDED_SOURCES, _guided_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All ten libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All eleven libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -130,6 +138,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, TRIANGULATE_LIB, TRIANGULATE_CSRC, TRIANGULATE_SOURCES, _triangulate_headers())
             if force or conv5x5_needs_build():
                 _build_locked(verbose, force, CONV5X5_LIB, CONV5X5_CSRC, CONV5X5_SOURCES, _conv5x5_headers())
+            if force or guided_needs_build():
+                _build_locked(verbose, force, GUIDED_LIB, GUIDED_CSRC, GUIDED_SOURCES, _guided_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -174,6 +184,10 @@ def _triangulate_headers():
 
 def _conv5x5_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_conv5x5.h")]
+
+
+def _guided_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_guided.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

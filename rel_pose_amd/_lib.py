@@ -191,6 +191,15 @@ CONV5X5_ABI_VERSION = _CONV5X5_CONSTS["RP_CONV5X5_ABI_VERSION"]
 CONV5X5_EXPORTS = tuple(_CONV5X5_PROTOTYPES)
 
 
+# the guided-matching library (include/relpose_guided.h -> librelpose_guided.so): the same parser, errcheck and RP_E* codes an eleventh time
+_GUIDED_LIB = None
+GUIDED_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_guided.h")
+with open(GUIDED_HEADER) as _f:
+    _GUIDED_CONSTS, _, _GUIDED_PROTOTYPES, _GUIDED_STATUS = _header_contract(_f.read(), "relpose_guided.h")
+GUIDED_ABI_VERSION = _GUIDED_CONSTS["RP_GUIDED_ABI_VERSION"]
+GUIDED_EXPORTS = tuple(_GUIDED_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -458,6 +467,32 @@ def load_conv5x5():
         if name in _CONV5X5_STATUS:
             fn.errcheck = _raise_on_status
     _CONV5X5_LIB = lib
+    return lib
+
+
+def load_guided():
+    """Load (building if absent or stale) and type librelpose_guided.so.  Raises on any failure: there is no fallback."""
+    global _GUIDED_LIB
+    if _GUIDED_LIB is not None:
+        return _GUIDED_LIB
+    path = _build.GUIDED_LIB
+    if _build.guided_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_guided_abi_version.restype = c_int
+    if lib.rp_guided_abi_version() != GUIDED_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_guided_abi_version(), GUIDED_ABI_VERSION))
+    for name, (res, args) in _GUIDED_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _GUIDED_STATUS:
+            fn.errcheck = _raise_on_status
+    _GUIDED_LIB = lib
     return lib
 
 

@@ -213,6 +213,30 @@ class ViTEss(nn.Module):
         from . import triangulate
         return triangulate.structure_from_matches(self, images, intrinsics, pose, chain, **chain_kwargs)
 
+    # -- guided matching (rel_pose_amd/guided.py; no counterpart in the reference) ----
+    def guided_correspondences(self, images, intrinsics, pose, band=1.5):
+        """The EMM's matches read again under `pose` [B,7]: per row and column the argmax over the tokens within `band` token pitches
+        of the pose's epipolar line (-1 where none is), its weight, the mass inside the band and the total mass, the mutual matches and
+        the in-band mass share per image and head -> guided.GuidedCorrespondences, usable by eightpoint.assemble_matches as it is.
+        eval() mode only; changes no module state and does not write to `intrinsics`."""
+        from . import guided
+        return guided.guided_correspondences(self, images, intrinsics, pose, band)
+
+    def pose_support(self, images, intrinsics, pose, band=1.5):
+        """[2B,3]: how much of what the EMM attends to `pose` explains -- the share of the attention's mass within `band` token pitches
+        of the pose's epipolar lines, per image and head.  Any two poses can be ranked by it.  eval() mode only."""
+        from . import guided
+        return guided.pose_support(self, images, intrinsics, pose, band)
+
+    def guided_pose_from_matches(self, images, intrinsics, prior="consensus", band=1.5, rounds=1, iters=10, heads=(0, 1, 2), tau=None,
+                                 subtoken=None, radius=2):
+        """Guided matching: prior ("consensus", "regressed" or a pose [B,7]) -> guided_correspondences -> assemble_matches ->
+        `iters` Levenberg-Marquardt iterations from the prior, `rounds` times -> guided.GuidedMatchPose with the support before and
+        after.  Guided matches lie near the prior's lines by construction: judge the result by its support, not by its Sampson cost.
+        eval() mode only; changes no module state and does not write to `intrinsics`."""
+        from . import guided
+        return guided.guided_pose_from_matches(self, images, intrinsics, prior, band, rounds, iters, heads, tau, subtoken, radius)
+
     def forward(self, images, Gs, intrinsics=None, inference=False):
         if not hasattr(Gs, "data") or isinstance(Gs, np.ndarray):
             Gs = SE3(torch.from_numpy(np.asarray(Gs)).unsqueeze(0).to(images.device).float())
