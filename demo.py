@@ -112,6 +112,12 @@ def main(argv=None):
                     help="with --eight_point: also solve the scene as ONE PLANE (rel_pose_amd/homography.py) -- the homography's inlier share "
                          "next to the essential chain's, the candidates of its decomposition with visibility and Sampson cost, and which "
                          "one is picked and why; --consensus M and --seed S set its hypotheses (default 256) and its sampler")
+    ap.add_argument("--rotation", action="store_true",
+                    help="with --eight_point: also solve the pair as a PURE ROTATION (rel_pose_amd/rotation.py) -- the rotation-only pose "
+                         "(t = 0), its robust cost and its inlier weight share, next to the inlier weight share of the eight-point consensus "
+                         "chain.  The two shares count different distances at the same tau -- the one-sided transfer distance under R "
+                         "against the Sampson distance to the epipolar line, which every match on the line passes -- so they are "
+                         "labelled, not compared by a threshold; --consensus M and --seed S set the hypotheses (default 256) and the sampler")
     ap.add_argument("--subtoken", choices=("window", "quadratic"), default=None,
                     help="with --eight_point or --matches: localise every match between the token centres (rel_pose_amd/readout.py, "
                          "subtoken_correspondences) -- the poses are then computed from those positions, the .npz also carries them")
@@ -140,6 +146,8 @@ def main(argv=None):
         ap.error("--consensus needs --eight_point")
     if args.planar and not args.eight_point:
         ap.error("--planar needs --eight_point")
+    if args.rotation and not args.eight_point:
+        ap.error("--rotation needs --eight_point")
     if args.minimal and not args.consensus:
         ap.error("--minimal needs --consensus")
     if args.consensus < 0:
@@ -179,6 +187,8 @@ def main(argv=None):
         print_eight_point(model, images, intr, png_size(args.img1), preds, args.refine, args.consensus, args.seed, args.subtoken, args.minimal or "eight")
         if args.planar:
             print_planar(model, images, intr, png_size(args.img1), args.consensus or 256, args.seed, args.subtoken)
+        if args.rotation:
+            print_rotation(model, images, intr, png_size(args.img1), preds, args.consensus or 256, args.seed, args.subtoken)
         if args.guided:
             print_guided(model, images, intr, png_size(args.img1), preds, est[0].data[:, 1], args.guided, args.prior or "consensus", args.subtoken)
         if args.points:
@@ -270,6 +280,21 @@ def print_planar(model, images, intr, orig_hw, hypotheses=256, seed=0, subtoken=
     else:
         print("planar: candidate %d, %s" % (pick[0], "the only one that sees the plane from both cameras" if cs[pick[0], 0] >= 0.99
                                              else "by Sampson cost: none sees every match"))
+
+
+def print_rotation(model, images, intr, orig_hw, regressed, hypotheses=256, seed=0, subtoken=None):
+    """--rotation: the pair solved as a pure rotation.  One pose line of the usual form (t = 0: the translation angle is printed as 90
+    degrees and means nothing), then one line with the robust cost and the inlier weight share of the refined rotation -- transfer
+    distance -- next to the inlier weight share of the eight-point consensus chain (the same hypotheses and seed) -- Sampson distance.
+    No threshold turns the share into a yes / no: the caller decides."""
+    H, W = images.shape[-2:]
+    sy, sx = H / orig_hw[0], W / orig_hw[1]
+    K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
+    rp = model.rotation_from_matches(images, K, hypotheses=hypotheses, seed=seed, subtoken=subtoken)
+    cp = model.consensus_pose_from_matches(images, K, hypotheses=hypotheses, seed=seed, refine=0, subtoken=subtoken)
+    _angles_line("rotation-only", rp.pose[0].double().cpu(), torch.from_numpy(np.asarray(regressed, dtype=np.float64)))
+    print("rotation-only: robust transfer cost %.6e, inlier weight share %.4f (transfer distance under R); eight-point consensus inlier "
+          "weight share %.4f (Sampson distance)" % (float(rp.stat[0, 0]), float(rp.stat[0, 1]), float(cp.consensus.stat[0, 1])))
 
 
 def print_guided(model, images, intr, orig_hw, regressed, regressed_raw, band, prior="consensus", subtoken=None):

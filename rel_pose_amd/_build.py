@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so, librelpose_triangulate.so, librelpose_conv5x5.so and librelpose_guided.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so, librelpose_triangulate.so, librelpose_conv5x5.so, librelpose_guided.so and librelpose_rotation.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -49,6 +49,10 @@ CONV5X5_SOURCES = ["conv5x5_dgrad_f32.hip"]
 GUIDED_CSRC = os.path.join(HERE, "csrc_guided")
 GUIDED_LIB = os.path.join(HERE, "librelpose_guided.so")
 GUIDED_SOURCES = ["emm_guided.hip"]
+# the pure-rotation library (include/relpose_rotation.h): a twelfth library, the same pattern
+ROTATION_CSRC = os.path.join(HERE, "csrc_rotation")
+ROTATION_LIB = os.path.join(HERE, "librelpose_rotation.so")
+ROTATION_SOURCES = ["rotation.hip"]
 ARCH = "gfx950"
 
 
@@ -110,10 +114,14 @@ def guided_needs_build():
     return _stale(GUIDED_LIB, GUIDED_CSRC, GUIDED_SOURCES, _guided_headers())
 
 
+def rotation_needs_build():
+    return _stale(ROTATION_LIB, ROTATION_CSRC, ROTATION_SOURCES, _rotation_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All eleven libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All twelve libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -140,6 +148,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, CONV5X5_LIB, CONV5X5_CSRC, CONV5X5_SOURCES, _conv5x5_headers())
             if force or guided_needs_build():
                 _build_locked(verbose, force, GUIDED_LIB, GUIDED_CSRC, GUIDED_SOURCES, _guided_headers())
+            if force or rotation_needs_build():
+                _build_locked(verbose, force, ROTATION_LIB, ROTATION_CSRC, ROTATION_SOURCES, _rotation_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -188,6 +198,10 @@ def _conv5x5_headers():
 
 def _guided_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_guided.h")]
+
+
+def _rotation_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_rotation.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

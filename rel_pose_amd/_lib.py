@@ -200,6 +200,16 @@ GUIDED_ABI_VERSION = _GUIDED_CONSTS["RP_GUIDED_ABI_VERSION"]
 GUIDED_EXPORTS = tuple(_GUIDED_PROTOTYPES)
 
 
+# the pure-rotation library (include/relpose_rotation.h -> librelpose_rotation.so): the same parser, errcheck and RP_E* codes a twelfth time
+_ROTATION_LIB = None
+ROTATION_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_rotation.h")
+with open(ROTATION_HEADER) as _f:
+    _ROTATION_CONSTS, _, _ROTATION_PROTOTYPES, _ROTATION_STATUS = _header_contract(_f.read(), "relpose_rotation.h")
+ROTATION_ABI_VERSION = _ROTATION_CONSTS["RP_ROTATION_ABI_VERSION"]
+ROTATION_MAX_P, ROTATION_MAX_M, ROTATION_MAX_ITERS = (_ROTATION_CONSTS[k] for k in ("RP_ROTATION_MAX_P", "RP_ROTATION_MAX_M", "RP_ROTATION_MAX_ITERS"))
+ROTATION_EXPORTS = tuple(_ROTATION_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -493,6 +503,32 @@ def load_guided():
         if name in _GUIDED_STATUS:
             fn.errcheck = _raise_on_status
     _GUIDED_LIB = lib
+    return lib
+
+
+def load_rotation():
+    """Load (building if absent or stale) and type librelpose_rotation.so.  Raises on any failure: there is no fallback."""
+    global _ROTATION_LIB
+    if _ROTATION_LIB is not None:
+        return _ROTATION_LIB
+    path = _build.ROTATION_LIB
+    if _build.rotation_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_rotation_abi_version.restype = c_int
+    if lib.rp_rotation_abi_version() != ROTATION_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_rotation_abi_version(), ROTATION_ABI_VERSION))
+    for name, (res, args) in _ROTATION_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _ROTATION_STATUS:
+            fn.errcheck = _raise_on_status
+    _ROTATION_LIB = lib
     return lib
 
 

@@ -204,6 +204,17 @@ class ViTEss(nn.Module):
         return homography.planar_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, refine, tau, subtoken, radius, vis_min,
                                                    prior)
 
+    def rotation_from_matches(self, images, intrinsics, heads=(0, 1, 2), hypotheses=256, seed=0, refine=10, tau=None, subtoken=None,
+                              radius=2):
+        """The rotation of a pair that ONLY ROTATES (a panorama crop), from the matches: with t = 0 every essential matrix fits, so the
+        chains above return a translation that means nothing.  `hypotheses` two-point rotation samples drawn from `seed`, each scored on
+        all matches; the best one polished by `refine` Levenberg-Marquardt iterations over its three parameters ->
+        rotation.RotationMatchPose, pose = (0, 0, 0, q).  Its stat[:, 1], the inlier weight share, is the evidence for "this pair only
+        rotates": near the share of good matches on a rotating pair, a few percent on a translating one.  The same seed gives the same
+        bits.  eval() mode only; changes no module state and does not write to `intrinsics`."""
+        from . import rotation
+        return rotation.rotation_from_matches(self, images, intrinsics, heads, hypotheses, seed, refine, tau, subtoken, radius)
+
     def structure_from_matches(self, images, intrinsics, pose=None, chain="refined", **chain_kwargs):
         """Where the POINTS are: the matches triangulated under a pose -> triangulate.MatchStructure, whose `structure` holds per match the
         point (frame of camera 1, units of the baseline), its depth in both cameras, the squared reprojection error and the parallax, and
