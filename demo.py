@@ -118,6 +118,11 @@ def main(argv=None):
                          "chain.  The two shares count different distances at the same tau -- the one-sided transfer distance under R "
                          "against the Sampson distance to the epipolar line, which every match on the line passes -- so they are "
                          "labelled, not compared by a threshold; --consensus M and --seed S set the hypotheses (default 256) and the sampler")
+    ap.add_argument("--auto", action="store_true",
+                    help="with --eight_point: let the matches CHOOSE between the essential matrix, the plane and the pure rotation "
+                         "(rel_pose_amd/select.py) -- the chosen model and its pose, one line per candidate with its criterion G, its "
+                         "inlier count and its inlier gate, and the estimated noise scale; --consensus M and --seed S set the hypotheses "
+                         "(default 1024 for the essential chain, 256 for the other two) and the sampler")
     ap.add_argument("--subtoken", choices=("window", "quadratic"), default=None,
                     help="with --eight_point or --matches: localise every match between the token centres (rel_pose_amd/readout.py, "
                          "subtoken_correspondences) -- the poses are then computed from those positions, the .npz also carries them")
@@ -148,6 +153,8 @@ def main(argv=None):
         ap.error("--planar needs --eight_point")
     if args.rotation and not args.eight_point:
         ap.error("--rotation needs --eight_point")
+    if args.auto and not args.eight_point:
+        ap.error("--auto needs --eight_point")
     if args.minimal and not args.consensus:
         ap.error("--minimal needs --consensus")
     if args.consensus < 0:
@@ -189,6 +196,9 @@ def main(argv=None):
             print_planar(model, images, intr, png_size(args.img1), args.consensus or 256, args.seed, args.subtoken)
         if args.rotation:
             print_rotation(model, images, intr, png_size(args.img1), preds, args.consensus or 256, args.seed, args.subtoken)
+        if args.auto:
+            print_auto(model, images, intr, png_size(args.img1), preds, args.consensus or (1024, 256, 256), args.seed, args.subtoken,
+                       args.minimal or "eight")
         if args.guided:
             print_guided(model, images, intr, png_size(args.img1), preds, est[0].data[:, 1], args.guided, args.prior or "consensus", args.subtoken)
         if args.points:
@@ -295,6 +305,31 @@ def print_rotation(model, images, intr, orig_hw, regressed, hypotheses=256, seed
     _angles_line("rotation-only", rp.pose[0].double().cpu(), torch.from_numpy(np.asarray(regressed, dtype=np.float64)))
     print("rotation-only: robust transfer cost %.6e, inlier weight share %.4f (transfer distance under R); eight-point consensus inlier "
           "weight share %.4f (Sampson distance)" % (float(rp.stat[0, 0]), float(rp.stat[0, 1]), float(cp.consensus.stat[0, 1])))
+
+
+def print_auto(model, images, intr, orig_hw, regressed, hypotheses=(1024, 256, 256), seed=0, subtoken=None, minimal="eight"):
+    """--auto: the model the matches support.  One line naming the chosen candidate and its kind, one pose line of the usual form for its
+    pose, one line per candidate with the criterion G, the inlier count and the inlier gate on e^2 (an invalid candidate says so), and
+    one with the noise scale and the candidate that supplied it."""
+    from rel_pose_amd import select
+    H, W = images.shape[-2:]
+    sy, sx = H / orig_hw[0], W / orig_hw[1]
+    K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
+    ap = model.auto_pose_from_matches(images, K, hypotheses=hypotheses, seed=seed, subtoken=subtoken, minimal=minimal)
+    pick, kind = int(ap.selection.pick[0]), int(ap.kind[0])
+    if pick < 0:
+        print("auto: no model (too few matches, or no candidate fits any of them)")
+    else:
+        print("auto: %s (candidate %d, %s)" % (select.KIND_NAMES[kind], pick, select.AUTO_NAMES[pick]))
+        _angles_line("auto", ap.pose[0].double().cpu(), torch.from_numpy(np.asarray(regressed, dtype=np.float64)))
+    st = ap.selection.stat[0].cpu()
+    for c, name in enumerate(select.AUTO_NAMES):
+        if pick < 0 or st[c, 0] >= 3e38:
+            print("auto candidate %d (%s): invalid" % (c, name))
+        else:
+            print("auto candidate %d (%s): G %.2f, %d inliers, gate %.6e" % (c, name, st[c, 0], int(st[c, 1]), st[c, 2]))
+    print("auto: sigma %.6e (%s)" % (float(ap.selection.scale[0, 0]),
+                                     "none" if pick < 0 else "given" if ap.selection.scale[0, 1] < 0 else "from candidate %d" % int(ap.selection.scale[0, 1])))
 
 
 def print_guided(model, images, intr, orig_hw, regressed, regressed_raw, band, prior="consensus", subtoken=None):

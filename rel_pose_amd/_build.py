@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so, librelpose_triangulate.so, librelpose_conv5x5.so, librelpose_guided.so and librelpose_rotation.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so, librelpose_triangulate.so, librelpose_conv5x5.so, librelpose_guided.so, librelpose_rotation.so and librelpose_select.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -53,6 +53,10 @@ GUIDED_SOURCES = ["emm_guided.hip"]
 ROTATION_CSRC = os.path.join(HERE, "csrc_rotation")
 ROTATION_LIB = os.path.join(HERE, "librelpose_rotation.so")
 ROTATION_SOURCES = ["rotation.hip"]
+# the model-selection library (include/relpose_select.h): a thirteenth library, the same pattern
+SELECT_CSRC = os.path.join(HERE, "csrc_select")
+SELECT_LIB = os.path.join(HERE, "librelpose_select.so")
+SELECT_SOURCES = ["select.hip"]
 ARCH = "gfx950"
 
 
@@ -118,10 +122,14 @@ def rotation_needs_build():
     return _stale(ROTATION_LIB, ROTATION_CSRC, ROTATION_SOURCES, _rotation_headers())
 
 
+def select_needs_build():
+    return _stale(SELECT_LIB, SELECT_CSRC, SELECT_SOURCES, _select_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All twelve libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All thirteen libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -150,6 +158,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, GUIDED_LIB, GUIDED_CSRC, GUIDED_SOURCES, _guided_headers())
             if force or rotation_needs_build():
                 _build_locked(verbose, force, ROTATION_LIB, ROTATION_CSRC, ROTATION_SOURCES, _rotation_headers())
+            if force or select_needs_build():
+                _build_locked(verbose, force, SELECT_LIB, SELECT_CSRC, SELECT_SOURCES, _select_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -202,6 +212,10 @@ def _guided_headers():
 
 def _rotation_headers():
     return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_rotation.h")]
+
+
+def _select_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_select.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

@@ -210,6 +210,16 @@ ROTATION_MAX_P, ROTATION_MAX_M, ROTATION_MAX_ITERS = (_ROTATION_CONSTS[k] for k 
 ROTATION_EXPORTS = tuple(_ROTATION_PROTOTYPES)
 
 
+# the model-selection library (include/relpose_select.h -> librelpose_select.so): the same parser, errcheck and RP_E* codes a thirteenth time
+_SELECT_LIB = None
+SELECT_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_select.h")
+with open(SELECT_HEADER) as _f:
+    _SELECT_CONSTS, _, _SELECT_PROTOTYPES, _SELECT_STATUS = _header_contract(_f.read(), "relpose_select.h")
+SELECT_ABI_VERSION = _SELECT_CONSTS["RP_SELECT_ABI_VERSION"]
+SELECT_MAX_P, SELECT_MAX_C = _SELECT_CONSTS["RP_SELECT_MAX_P"], _SELECT_CONSTS["RP_SELECT_MAX_C"]
+SELECT_EXPORTS = tuple(_SELECT_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -529,6 +539,32 @@ def load_rotation():
         if name in _ROTATION_STATUS:
             fn.errcheck = _raise_on_status
     _ROTATION_LIB = lib
+    return lib
+
+
+def load_select():
+    """Load (building if absent or stale) and type librelpose_select.so.  Raises on any failure: there is no fallback."""
+    global _SELECT_LIB
+    if _SELECT_LIB is not None:
+        return _SELECT_LIB
+    path = _build.SELECT_LIB
+    if _build.select_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_select_abi_version.restype = c_int
+    if lib.rp_select_abi_version() != SELECT_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_select_abi_version(), SELECT_ABI_VERSION))
+    for name, (res, args) in _SELECT_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _SELECT_STATUS:
+            fn.errcheck = _raise_on_status
+    _SELECT_LIB = lib
     return lib
 
 

@@ -215,6 +215,19 @@ class ViTEss(nn.Module):
         from . import rotation
         return rotation.rotation_from_matches(self, images, intrinsics, heads, hypotheses, seed, refine, tau, subtoken, radius)
 
+    def auto_pose_from_matches(self, images, intrinsics, heads=(0, 1, 2), hypotheses=(1024, 256, 256), seed=0, refine=10, tau=None,
+                               sigma=None, subtoken=None, radius=2, minimal="eight"):
+        """WHICH of the three chains above to believe, decided from the matches themselves: the consensus chain, the planar chain and the
+        rotation chain run on the same matches, and an information criterion (select.model_select) compares five
+        candidates -- the E of the refined consensus pose, the E of the planar chain's two picks after `refine` iterations, H and R -- on
+        one scale: the Sampson residuals under each, a noise scale estimated from the residuals (sigma: given instead), and an outlier
+        that costs the same under every model -> select.AutoMatchPose: `kind` 0 essential, 1 homography, 2 rotation (-1: none) and the
+        `pose` of the chosen model -- for H the planar chain's first pick, for R (0, 0, 0, q).  hypotheses: one number, or (consensus,
+        planar, rotation).  The same seed gives the same bits.  eval() mode only; changes no module state and does not write to
+        `intrinsics`."""
+        from . import select
+        return select.auto_pose_from_matches(self, images, intrinsics, heads, hypotheses, seed, refine, tau, sigma, subtoken, radius, minimal)
+
     def structure_from_matches(self, images, intrinsics, pose=None, chain="refined", **chain_kwargs):
         """Where the POINTS are: the matches triangulated under a pose -> triangulate.MatchStructure, whose `structure` holds per match the
         point (frame of camera 1, units of the baseline), its depth in both cameras, the squared reprojection error and the parallax, and
