@@ -123,6 +123,11 @@ def main(argv=None):
                          "(rel_pose_amd/select.py) -- the chosen model and its pose, one line per candidate with its criterion G, its "
                          "inlier count and its inlier gate, and the estimated noise scale; --consensus M and --seed S set the hypotheses "
                          "(default 1024 for the essential chain, 256 for the other two) and the sampler")
+    ap.add_argument("--uncertainty", action="store_true",
+                    help="with --eight_point: the pose of the chosen chain (the consensus chain with --consensus M, else the refined one) "
+                         "with its standard deviations -- rotation +- x deg, translation direction +- y deg --, the least determined "
+                         "direction and how many matches lie beyond tau (rel_pose_amd/covariance.py); 'not determined' where the "
+                         "matches do not fix the pose")
     ap.add_argument("--subtoken", choices=("window", "quadratic"), default=None,
                     help="with --eight_point or --matches: localise every match between the token centres (rel_pose_amd/readout.py, "
                          "subtoken_correspondences) -- the poses are then computed from those positions, the .npz also carries them")
@@ -155,6 +160,8 @@ def main(argv=None):
         ap.error("--rotation needs --eight_point")
     if args.auto and not args.eight_point:
         ap.error("--auto needs --eight_point")
+    if args.uncertainty and not args.eight_point:
+        ap.error("--uncertainty needs --eight_point")
     if args.minimal and not args.consensus:
         ap.error("--minimal needs --consensus")
     if args.consensus < 0:
@@ -199,6 +206,9 @@ def main(argv=None):
         if args.auto:
             print_auto(model, images, intr, png_size(args.img1), preds, args.consensus or (1024, 256, 256), args.seed, args.subtoken,
                        args.minimal or "eight")
+        if args.uncertainty:
+            print_uncertainty(model, images, intr, png_size(args.img1), preds, args.refine or 10, args.consensus, args.seed, args.subtoken,
+                              args.minimal or "eight")
         if args.guided:
             print_guided(model, images, intr, png_size(args.img1), preds, est[0].data[:, 1], args.guided, args.prior or "consensus", args.subtoken)
         if args.points:
@@ -330,6 +340,32 @@ def print_auto(model, images, intr, orig_hw, regressed, hypotheses=(1024, 256, 2
             print("auto candidate %d (%s): G %.2f, %d inliers, gate %.6e" % (c, name, st[c, 0], int(st[c, 1]), st[c, 2]))
     print("auto: sigma %.6e (%s)" % (float(ap.selection.scale[0, 0]),
                                      "none" if pick < 0 else "given" if ap.selection.scale[0, 1] < 0 else "from candidate %d" % int(ap.selection.scale[0, 1])))
+
+
+def print_uncertainty(model, images, intr, orig_hw, regressed, refine=10, consensus=0, seed=0, subtoken=None, minimal="eight"):
+    """--uncertainty: the pose of the chosen chain -- the consensus chain with --consensus M, else the refined one -- in the usual form,
+    then its standard deviations from the sandwich covariance of the robust fit (rel_pose_amd/covariance.py), the least determined
+    direction of (omega_0, omega_1, omega_2, beta_1, beta_2), and one line with rho (the smallest pivot of the scaled A, near 0: a
+    direction the matches do not fix), the rows beyond tau and the rows of positive weight.  Status -1 prints "not determined" in the
+    place of the numbers, status 0 "degenerate"."""
+    from rel_pose_amd import covariance
+    H, W = images.shape[-2:]
+    sy, sx = H / orig_hw[0], W / orig_hw[1]
+    K = torch.tensor([intr], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
+    kw = dict(hypotheses=consensus, seed=seed, minimal=minimal) if consensus else {}
+    chain = "consensus" if consensus else "refined"
+    res, pc = model.pose_uncertainty_from_matches(images, K, chain=chain, refine=refine, subtoken=subtoken, **kw)
+    _angles_line("uncertainty (%s chain)" % chain, res.pose[0].double().cpu(), torch.from_numpy(np.asarray(regressed, dtype=np.float64)))
+    st = pc.stat[0].cpu().tolist()
+    if st[0] == covariance.OK:
+        print("uncertainty: rotation +- %.4f deg, translation direction +- %.4f deg"
+              % (float(covariance.rotation_sd_deg(pc)[0]), float(covariance.direction_sd_deg(pc)[0])))
+        print("uncertainty: weak direction (w0 w1 w2 b1 b2) %s, +- %.4f deg along it"
+              % (" ".join("%.4f" % v for v in pc.weak[0].cpu().tolist()), np.degrees(max(float(pc.eig[0, 0]), 0.0) ** 0.5)))
+    else:
+        print("uncertainty: %s" % ("not determined (the matches do not fix the pose at this tau)" if st[0] == covariance.NOT_DETERMINED
+                                    else "degenerate (too few matches, or no pose)"))
+    print("uncertainty: rho %.3e, %d of %d weighted matches beyond tau, robust cost %.6e" % (st[4], int(st[5]), int(st[1]), st[6]))
 
 
 def print_guided(model, images, intr, orig_hw, regressed, regressed_raw, band, prior="consensus", subtoken=None):

@@ -220,6 +220,16 @@ SELECT_MAX_P, SELECT_MAX_C = _SELECT_CONSTS["RP_SELECT_MAX_P"], _SELECT_CONSTS["
 SELECT_EXPORTS = tuple(_SELECT_PROTOTYPES)
 
 
+# the pose-covariance library (include/relpose_covariance.h -> librelpose_covariance.so): the same parser, errcheck and RP_E* codes a fourteenth time
+_COVARIANCE_LIB = None
+COVARIANCE_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_covariance.h")
+with open(COVARIANCE_HEADER) as _f:
+    _COVARIANCE_CONSTS, _, _COVARIANCE_PROTOTYPES, _COVARIANCE_STATUS = _header_contract(_f.read(), "relpose_covariance.h")
+COVARIANCE_ABI_VERSION = _COVARIANCE_CONSTS["RP_COVARIANCE_ABI_VERSION"]
+COVARIANCE_MAX_P, COVARIANCE_SWEEPS = _COVARIANCE_CONSTS["RP_COVARIANCE_MAX_P"], _COVARIANCE_CONSTS["RP_COVARIANCE_SWEEPS"]
+COVARIANCE_EXPORTS = tuple(_COVARIANCE_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -565,6 +575,32 @@ def load_select():
         if name in _SELECT_STATUS:
             fn.errcheck = _raise_on_status
     _SELECT_LIB = lib
+    return lib
+
+
+def load_covariance():
+    """Load (building if absent or stale) and type librelpose_covariance.so.  Raises on any failure: there is no fallback."""
+    global _COVARIANCE_LIB
+    if _COVARIANCE_LIB is not None:
+        return _COVARIANCE_LIB
+    path = _build.COVARIANCE_LIB
+    if _build.covariance_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_covariance_abi_version.restype = c_int
+    if lib.rp_covariance_abi_version() != COVARIANCE_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_covariance_abi_version(), COVARIANCE_ABI_VERSION))
+    for name, (res, args) in _COVARIANCE_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _COVARIANCE_STATUS:
+            fn.errcheck = _raise_on_status
+    _COVARIANCE_LIB = lib
     return lib
 
 

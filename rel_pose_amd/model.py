@@ -237,6 +237,17 @@ class ViTEss(nn.Module):
         from . import triangulate
         return triangulate.structure_from_matches(self, images, intrinsics, pose, chain, **chain_kwargs)
 
+    def pose_uncertainty_from_matches(self, images, intrinsics, pose=None, chain="consensus", **chain_kwargs):
+        """HOW WELL the matches determine the pose: the covariance of the refined pose's five parameters (three rotation angles, two
+        angles of the direction of t) as the sandwich estimate of the robust fit (covariance.pose_covariance), on the
+        same matches, base weights and tau the chain's refinement used -> (what the chain returned, covariance.PoseCovariance): the
+        standard deviations of the rotation and of the direction, the least determined direction, and a status that says "not
+        determined" instead of a number where the matches do not fix the pose.  The pose is that of the chain `chain` -- "eight",
+        "refined", "consensus" or "planar" (its first pick), run with `chain_kwargs` -- or the given `pose` [B,7] as it is.  eval() mode
+        only; changes no module state and does not write to `intrinsics`."""
+        from . import covariance
+        return covariance.pose_uncertainty_from_matches(self, images, intrinsics, pose, chain, **chain_kwargs)
+
     # -- guided matching (rel_pose_amd/guided.py; no counterpart in the reference) ----
     def guided_correspondences(self, images, intrinsics, pose, band=1.5):
         """The EMM's matches read again under `pose` [B,7]: per row and column the argmax over the tokens within `band` token pitches
