@@ -140,6 +140,10 @@ def main(argv=None):
                     help="with --eight_point: guided matching (rel_pose_amd/guided.py) -- every token's partner searched again within BAND "
                          "token pitches of the prior's epipolar lines, the pose refined on those matches; prints the guided pose and the "
                          "share of the attention's mass that the regressed, the consensus and the guided pose explain, on one scale")
+    ap.add_argument("--third", metavar="IMG3", default="",
+                    help="with --eight_point: the pose of a THIRD image against the structure of (img1, img2) (rel_pose_amd/resection.py) -- "
+                         "its translation is in units of the baseline of (img1, img2), so the line 'baseline ratio' chains the two pairs; "
+                         "the rotation and direction are compared with the two-view chain's for (img1, IMG3)")
     ap.add_argument("--prior", choices=("consensus", "regressed"), default=None, help="with --guided: the pose that guides (default consensus)")
     args = ap.parse_args(argv)
     if args.guided and not args.eight_point:
@@ -148,6 +152,8 @@ def main(argv=None):
         ap.error("--guided takes a positive band in token pitches")
     if args.prior and not args.guided:
         ap.error("--prior needs --guided")
+    if args.third and not args.eight_point:
+        ap.error("--third needs --eight_point")
     if args.points and not args.eight_point:
         ap.error("--points needs --eight_point")
     if args.subtoken and not (args.eight_point or args.matches):
@@ -211,6 +217,10 @@ def main(argv=None):
                               args.minimal or "eight")
         if args.guided:
             print_guided(model, images, intr, png_size(args.img1), preds, est[0].data[:, 1], args.guided, args.prior or "consensus", args.subtoken)
+        if args.third:
+            third = load_pair(args.img1, args.third, matterport)[:, 1:].cuda()
+            print_third(model, torch.cat([images, third], 1), intr, png_size(args.img1), args.consensus or 256, args.seed, args.refine or 10,
+                        args.subtoken)
         if args.points:
             write_points(model, images, intr, png_size(args.img1), args.points, args.refine or 10, args.consensus, args.seed, args.subtoken,
                          args.minimal or "eight")
@@ -315,6 +325,29 @@ def print_rotation(model, images, intr, orig_hw, regressed, hypotheses=256, seed
     _angles_line("rotation-only", rp.pose[0].double().cpu(), torch.from_numpy(np.asarray(regressed, dtype=np.float64)))
     print("rotation-only: robust transfer cost %.6e, inlier weight share %.4f (transfer distance under R); eight-point consensus inlier "
           "weight share %.4f (Sampson distance)" % (float(rp.stat[0, 0]), float(rp.stat[0, 1]), float(cp.consensus.stat[0, 1])))
+
+
+def print_third(model, images3, intr, orig_hw, hypotheses=256, seed=0, iters=10, subtoken=None):
+    """--third IMG3: the third image against the structure of (img1, img2).  One pose line of the usual format for IMG3 (t in units of the
+    baseline of (img1, img2), NOT normalised), the baseline ratio, the inlier weight share of the resection, and the angles between the
+    resection's rotation / translation direction and those of the two-view consensus chain for (img1, IMG3); a degenerate result (too
+    few usable points, or no valid hypothesis) says `not determined` instead."""
+    H, W = images3.shape[-2:]
+    sy, sx = H / orig_hw[0], W / orig_hw[1]
+    K = torch.tensor([[intr[0], intr[1], intr[1]]], dtype=torch.float32).cuda() * torch.tensor([sx, sy, sx, sy]).cuda()
+    kw = dict(subtoken=subtoken) if subtoken else {}
+    tv = model.third_view_pose_from_matches(images3, K, hypotheses=hypotheses, seed=seed, iters=iters, **kw)
+    pose, two = tv.pose_c[0].double().cpu(), tv.two_view_c.pose[0].double().cpu()
+    scale = float(tv.scale[0])
+    if not scale > 0 or not bool(torch.isfinite(pose).all()) or float(tv.stat[0, 3]) < 3:
+        print("third view: not determined (%d usable points)" % int(tv.stat[0, 3]))
+        return
+    dq = min(1.0, abs(float((pose[3:] * two[3:]).sum())))
+    dt = max(-1.0, min(1.0, float((pose[:3] * two[:3]).sum()) / max(scale * float(two[:3].norm()), 1e-30)))
+    print("third view pose x,y,z,qx,qy,qz,qw: %s" % " ".join("%.5f" % v for v in pose.tolist()))
+    print("third view: baseline ratio |t_c| / |t_a| = %.5f ; inlier weight share %.4f over %d points ; against the two-view chain for "
+          "(img1, img3): rotation differs by %.3f deg, translation direction by %.3f deg"
+          % (scale, float(tv.stat[0, 1]), int(tv.stat[0, 3]), 2 * np.degrees(np.arccos(dq)), np.degrees(np.arccos(dt))))
 
 
 def print_auto(model, images, intr, orig_hw, regressed, hypotheses=(1024, 256, 256), seed=0, subtoken=None, minimal="eight"):

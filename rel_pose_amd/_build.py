@@ -1,4 +1,4 @@
-"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so, librelpose_triangulate.so, librelpose_conv5x5.so, librelpose_guided.so, librelpose_rotation.so, librelpose_select.so and librelpose_covariance.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
+"""Build librelpose_hip.so, librelpose_readout.so, librelpose_eightpoint.so, librelpose_refine.so, librelpose_consensus.so, librelpose_submatch.so, librelpose_fivepoint.so, librelpose_homography.so, librelpose_triangulate.so, librelpose_conv5x5.so, librelpose_guided.so, librelpose_rotation.so, librelpose_select.so, librelpose_covariance.so and librelpose_resection.so (gfx950) in-tree with hipcc.  No CPU fallback exists: if the build or
 the load fails, every op in rel_pose_amd raises."""
 import os
 import subprocess
@@ -61,6 +61,10 @@ SELECT_SOURCES = ["select.hip"]
 COVARIANCE_CSRC = os.path.join(HERE, "csrc_covariance")
 COVARIANCE_LIB = os.path.join(HERE, "librelpose_covariance.so")
 COVARIANCE_SOURCES = ["covariance.hip"]
+# the resection library (include/relpose_resection.h): a fifteenth library, the same pattern
+RESECTION_CSRC = os.path.join(HERE, "csrc_resection")
+RESECTION_LIB = os.path.join(HERE, "librelpose_resection.so")
+RESECTION_SOURCES = ["resection.hip"]
 ARCH = "gfx950"
 
 
@@ -134,10 +138,14 @@ def covariance_needs_build():
     return _stale(COVARIANCE_LIB, COVARIANCE_CSRC, COVARIANCE_SOURCES, _covariance_headers())
 
 
+def resection_needs_build():
+    return _stale(RESECTION_LIB, RESECTION_CSRC, RESECTION_SOURCES, _resection_headers())
+
+
 def build(force=False, verbose=True):
     """Compile under an exclusive file lock (eight ranks of a first `torchrun` would otherwise write the same .o / .so at
     once) and move the finished library into place atomically, so a concurrent loader never maps a half-written file.
-    All fourteen libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
+    All fifteen libraries are built under the one lock, each only if it is stale (force: all, every translation unit)."""
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -170,6 +178,8 @@ def build(force=False, verbose=True):
                 _build_locked(verbose, force, SELECT_LIB, SELECT_CSRC, SELECT_SOURCES, _select_headers())
             if force or covariance_needs_build():
                 _build_locked(verbose, force, COVARIANCE_LIB, COVARIANCE_CSRC, COVARIANCE_SOURCES, _covariance_headers())
+            if force or resection_needs_build():
+                _build_locked(verbose, force, RESECTION_LIB, RESECTION_CSRC, RESECTION_SOURCES, _resection_headers())
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -230,6 +240,10 @@ def _select_headers():
 
 def _covariance_headers():
     return _headers() + [os.path.join(COVARIANCE_CSRC, "sym5.h"), os.path.join(os.path.dirname(HERE), "include", "relpose_covariance.h")]
+
+
+def _resection_headers():
+    return _headers() + [os.path.join(os.path.dirname(HERE), "include", "relpose_resection.h")]
 
 
 def _build_locked(verbose, force, lib, csrc, sources, headers):

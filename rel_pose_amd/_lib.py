@@ -230,6 +230,16 @@ COVARIANCE_MAX_P, COVARIANCE_SWEEPS = _COVARIANCE_CONSTS["RP_COVARIANCE_MAX_P"],
 COVARIANCE_EXPORTS = tuple(_COVARIANCE_PROTOTYPES)
 
 
+# the resection library (include/relpose_resection.h -> librelpose_resection.so): the same parser, errcheck and RP_E* codes a fifteenth time
+_RESECTION_LIB = None
+RESECTION_HEADER = os.path.join(os.path.dirname(HEADER), "relpose_resection.h")
+with open(RESECTION_HEADER) as _f:
+    _RESECTION_CONSTS, _, _RESECTION_PROTOTYPES, _RESECTION_STATUS = _header_contract(_f.read(), "relpose_resection.h")
+RESECTION_ABI_VERSION = _RESECTION_CONSTS["RP_RESECTION_ABI_VERSION"]
+RESECTION_MAX_P, RESECTION_MAX_M, RESECTION_MAX_ITERS = (_RESECTION_CONSTS[k] for k in ("RP_RESECTION_MAX_P", "RP_RESECTION_MAX_M", "RP_RESECTION_MAX_ITERS"))
+RESECTION_EXPORTS = tuple(_RESECTION_PROTOTYPES)
+
+
 def lib_path():
     return _build.LIB
 
@@ -601,6 +611,32 @@ def load_covariance():
         if name in _COVARIANCE_STATUS:
             fn.errcheck = _raise_on_status
     _COVARIANCE_LIB = lib
+    return lib
+
+
+def load_resection():
+    """Load (building if absent or stale) and type librelpose_resection.so.  Raises on any failure: there is no fallback."""
+    global _RESECTION_LIB
+    if _RESECTION_LIB is not None:
+        return _RESECTION_LIB
+    path = _build.RESECTION_LIB
+    if _build.resection_needs_build():
+        _build.build(verbose=False)
+    try:
+        lib = ctypes.CDLL(path)
+    except OSError as e:
+        raise RuntimeError("rel_pose_amd: cannot load HIP extension %s (%s); there is no CPU fallback" % (path, e))
+    lib.rp_resection_abi_version.restype = c_int
+    if lib.rp_resection_abi_version() != RESECTION_ABI_VERSION:
+        raise RuntimeError("rel_pose_amd: %s has ABI version %d, this package binds version %d -- rebuild with "
+                           "`python -m rel_pose_amd._build --force`" % (path, lib.rp_resection_abi_version(), RESECTION_ABI_VERSION))
+    for name, (res, args) in _RESECTION_PROTOTYPES.items():
+        fn = getattr(lib, name)          # AttributeError = symbol missing = broken build
+        fn.restype = res
+        fn.argtypes = args
+        if name in _RESECTION_STATUS:
+            fn.errcheck = _raise_on_status
+    _RESECTION_LIB = lib
     return lib
 
 

@@ -248,6 +248,16 @@ class ViTEss(nn.Module):
         from . import covariance
         return covariance.pose_uncertainty_from_matches(self, images, intrinsics, pose, chain, **chain_kwargs)
 
+    def third_view_pose_from_matches(self, images, intrinsics, chain="consensus", hypotheses=256, seed=0, iters=10, min_parallax=None,
+                                     **chain_kwargs):
+        """WHERE a THIRD camera is, in units of the first pair's baseline: images [B,3,3,H,W] = (hub, a, c), intrinsics [B,3,4].  The
+        matches of (hub, a) are triangulated under the pose of the chain `chain`, and the pose of c is fitted to those points and to the
+        matches of (hub, c) -- row p of both pairs is the same token of the hub -- by three-point consensus and a six-parameter polish
+        (resection.third_view_pose) -> resection.ThirdView, whose `scale` = |t_c| is the ratio of the two baselines.
+        eval() mode only; changes no module state and does not write to `intrinsics`."""
+        from . import resection
+        return resection.third_view_pose(self, images, intrinsics, chain, hypotheses, seed, iters, min_parallax, **chain_kwargs)
+
     # -- guided matching (rel_pose_amd/guided.py; no counterpart in the reference) ----
     def guided_correspondences(self, images, intrinsics, pose, band=1.5):
         """The EMM's matches read again under `pose` [B,7]: per row and column the argmax over the tokens within `band` token pitches
